@@ -20,6 +20,13 @@ device generators (verification by the key/FK pair identity).
 
 value = probe tuples/s (all ranks' probe tuples / max over ranks of the probe-phase time, the
 reference's t_probeStr); build_ms is reported beside it. ms_per_step = wall time per step.
+
+A plain run sets up, runs the warmup steps, times --steps steps and prints the result line (metric,
+value, ms_per_step, the phase times and the configuration). --dump-outputs DIR also writes what the
+last timed step computed (counters.npy; out_pairs.npy, a seeded sample of the sorted output pairs)
+for output-for-output comparison of two builds. --full adds everything beside the headline figure:
+kernel-timing steps and the roofline, the verification step against the reference's fixture (the run
+fails if it differs), repeat_mintime, the same-run copy peak and the CPU baseline.
 """
 import argparse
 import json
@@ -93,12 +100,22 @@ def parse():
                         "device: seeded device generators (checked by the key/FK pair identity)")
     p.add_argument("--b", type=int, default=1, help="bucket scale-down (#buckets = |R| / b)")
     p.add_argument("--no-emit", action="store_true", help="aggregate-only probe (no pair materialisation)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything beside the headline figure: the kernel-timing "
+                        "steps and the roofline, the verification step against the reference's fixture, the "
+                        "repeat_mintime figure, the same-run copy peak and the CPU baseline (a plain run sets up, "
+                        "warms up, times the steps and prints the result line)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step computed to DIR/<name>.npy (float64; the output pairs sorted, "
+                        "a fixed, seeded sample of their rows)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--cpu-sample", type=int, default=20_000_000,
                    help="config B: the CPU baseline probes this prefix of the identical S relation")
     p.add_argument("--cpu-reps", type=int, default=8, help="CPU baseline: repeat_mintime minimum repetitions")
-    p.add_argument("--no-mintime", action="store_true", help="skip the repeat_mintime figure")
-    p.add_argument("--pmc-json", default=latest_pmc(), help="PMC summary (scripts/pmc_summary.py) for roofline.traffic")
+    p.add_argument("--no-mintime", action="store_true", help="--full without the repeat_mintime figure")
+    p.add_argument("--pmc-json", default=None,
+                   help="--full: PMC summary (scripts/pmc_summary.py) for roofline.traffic (default: the best match "
+                        "under profiles/)")
     p.add_argument("--json-out", default=None)
     p.add_argument("--chunks", type=int, default=4,
                    help="N>1: S is exchanged in this many chunks, each chunk's all-to-all overlapping the "
@@ -139,6 +156,10 @@ def parse():
                         "packed probe), 1 (every timer) for the other B/D probe paths, 0 for C/E (no timer read)")
     p.add_argument("--log2R", type=int, default=22, help="config E: |R| = 2^log2R")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    if a.full and a.pmc_json is None:
+        a.pmc_json = latest_pmc()
     if a.workload is None:
         a.workload = "B" if a.gpus == 1 else "D"
     return a
@@ -339,6 +360,33 @@ def _events(torch, n):
         import hj3d
         return [hj3d.TimingEvent(_EVENT_CTX) for _ in range(n)]
     return [torch.cuda.Event(enable_timing=True) for _ in range(n)]
+
+
+DUMP_ROWS = 2_000_000  # sampled output rows of --dump-outputs (2 float64 words each: 32 MB)
+DUMP_SEED = 0x5eed0d0
+DUMP_MAX_BYTES = 64 << 20
+
+
+def sample_pairs(torch, out, n_rows):
+    """--dump-outputs: the first n_rows rows of the (n, 2) u32 pair array `out` (device) as float64
+    on the host, sorted by (first, second) word: the pairs are a set, and the order the kernels
+    leave them in (partition order, atomics) differs from run to run. Of more than DUMP_ROWS rows
+    a fixed sample of the sorted rows (seeded row indices, ascending)."""
+    rows = out[:n_rows].to(torch.int64) & 0xFFFFFFFF
+    key, _ = torch.sort((rows[:, 0] << 32) | rows[:, 1])
+    del rows
+    if n_rows > DUMP_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n_rows, DUMP_ROWS))
+        key = key[torch.from_numpy(idx).to(key.device)]
+    return torch.stack(((key >> 32) & 0xFFFFFFFF, key & 0xFFFFFFFF), dim=1).cpu().numpy().astype(np.float64)
+
+
+def dump_outputs(d, arrays, suffix=""):
+    """--dump-outputs DIR: DIR/<name><suffix>.npy, float64, at most DUMP_MAX_BYTES in all."""
+    os.makedirs(d, exist_ok=True)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def _emit(line, args):
@@ -590,6 +638,79 @@ def main():
 
     build_ms = sum(e[0].elapsed_time(e[1]) for e in evs) / args.steps
     probe_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / args.steps
+    wall_ms = wall * 1e3 / args.steps
+    if args.dump_outputs:
+        # the last timed step's result, before any later step writes `out` again: the counters of
+        # its probe strand and the materialised pairs (unique chaining: one slot per probe tuple of
+        # this rank; unnest: the strand's output count)
+        r = ctx.probe_result()
+        arrays = {"counters": np.array([r.n_probe, r.n_matched, r.n_out, r.n_cmps], dtype=np.float64)}
+        if emit:
+            n_rows = state.get("probe_n", nS) if unique else r.n_out
+            arrays["out_pairs"] = sample_pairs(torch, out, min(n_rows, out.shape[0]))
+        dump_outputs(args.dump_outputs, arrays, f".rank{rank}" if world > 1 else "")
+
+    if unique:
+        metric, unit = METRIC, "probe tuples/s"
+    else:
+        metric, unit = (f"unnested output tuples/s (probe + unnest phase), exp1 key/FK plan {plan}",
+                        "output tuples/s")
+    if args.workload == "B":
+        workload = f"exp1 key/FK plan {plan}, |R|={nR_tot // world} |S|={nS_tot // world} per GPU, uniform FKs, b={args.b}"
+    else:
+        workload = (f"config D: exp1 key/FK plan {plan}, |R|={nR_tot} |S|={nS_tot} in total over {world} GPU(s) "
+                    f"(|R|={nR} |S|={nS} on rank 0), uniform FKs, b={args.b}")
+
+    def headline(build_ms, probe_ms, wall_ms):
+        """The result line of a plain run (a --full line adds to it): the figures of the timed steps."""
+        line = {
+            "metric": metric,
+            "value": nS_tot / (probe_ms * 1e-3),  # |S| probe tuples (Csr) = |S| output pairs (every plan)
+            "unit": unit,
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": wall_ms,
+            "higher_is_better": True,
+            "scaling": scaling,
+            "vs_baseline": None,
+            "dtype": "u32",
+            "data": data,
+            "config": {
+                "workload": workload, "config": args.workload,
+                "plan": plan, "R_total": nR_tot, "S_total": nS_tot, "R_per_gpu": nR_tot // world,
+                "S_per_gpu": nS_tot // world, "num_buckets": nb, "num_dv_Sa": dv,
+                "emit_pairs": emit, "parallelism": f"bucket-range partition x{world}" if sharded else "single GPU",
+                "exchange_chunks": (C if sharded else None),
+                "exchange_partitioner": ((("single-pass hj3d_partition_strided" if args.xpart == "single" else
+                                           "stable two-pass hj3d_partition") + " (probe side); stable (build side)")
+                                         if sharded else None),
+                "exchange": ("libhj3d hj3d_comm_* over RCCL" if sharded and not args.rehearse else
+                             "torch.distributed gloo, host-staged (rehearsal)" if sharded else None),
+                "rehearsal_one_gpu": bool(args.rehearse),
+                # the packed probe's LDS-slice geometry on this rank: P slices of W buckets; C > 1 = two
+                # partition levels (k_pk_part into P1 ranges of C slices, k_pk_split by slice)
+                "probe_slices": ctx.pk_plan(max(nb // world, 1), max(nB, 1)) if packed else None,
+            },
+            "build_ms": build_ms,
+            "probe_ms": probe_ms,
+            "join_tuples_per_s": nS_tot / ((build_ms + probe_ms) * 1e-3),
+            "input_generation_s": gen_s,
+        }
+        if sharded:
+            line["config"]["probe_send_pairs"] = sum(int(t.shape[0]) for t in sendP_c) if single else nP
+            line["config"]["probe_spilled_chunks"] = sorted(spill)
+        return line
+
+    if not args.full:
+        if world > 1:
+            build_ms, probe_ms, wall_ms = (hdist.allreduce_max(v, dev) for v in (build_ms, probe_ms, wall_ms))
+        if rank == 0:
+            _emit(headline(build_ms, probe_ms, wall_ms), args)
+        teardown()
+        return
+
+    # ---- --full: kernel timing, verification, repeat_mintime, roofline, copy peak, CPU baseline ----
     instrumented = None
     if timed_timing != lib_timing:
         # K kernel-timing steps: the same step with the per-kernel events (HIP events on the engine's
@@ -623,7 +744,6 @@ def main():
     torch.cuda.synchronize()
     res = ctx.probe_result()
     st = table.stats()
-    wall_ms = wall * 1e3 / args.steps
     probe_n_local = state.get("probe_n", nP)
 
     # repeat_mintime (util/measure_helpers.hh:15-41 as main_experiment1.cc:663-699 uses it): >= 8
@@ -752,16 +872,6 @@ def main():
     # the whole probe phase (partition + probe; N > 1: + exchange) against SURVEY §8(d): 20 B per
     # probe tuple + per output 8 B (chaining) or 4 + 8 B (unnest: sub row read, pair write)
     phase_alg = probe_n_local * (tuple_bytes + 8) + (nS_tot // world) * ((8 if emit else 0) + (0 if unique else 4))
-    if unique:
-        metric, unit = METRIC, "probe tuples/s"
-    else:
-        metric, unit = (f"unnested output tuples/s (probe + unnest phase), exp1 key/FK plan {plan}",
-                        "output tuples/s")
-    if args.workload == "B":
-        workload = f"exp1 key/FK plan {plan}, |R|={nR_tot // world} |S|={nS_tot // world} per GPU, uniform FKs, b={args.b}"
-    else:
-        workload = (f"config D: exp1 key/FK plan {plan}, |R|={nR_tot} |S|={nS_tot} in total over {world} GPU(s) "
-                    f"(|R|={nR} |S|={nS} on rank 0), uniform FKs, b={args.b}")
 
     # The roofline's unit. Unique chaining (Csr): the longer of the two timed probe-phase kernels, which
     # are the step's largest. The 3D plans: the step's largest kernels are the build's aggregation
@@ -784,38 +894,7 @@ def main():
                                 "achieved_GBs": build_alg / (build_ms * 1e-3) / 1e9,
                                 "frac": build_alg / (build_ms * 1e-3) / 1e9 / PEAK_HBM_GBS}}
     line = {
-        "metric": metric,
-        "value": nS_tot / (probe_ms * 1e-3),  # |S| probe tuples (Csr) = |S| output pairs (every plan)
-        "unit": unit,
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": wall_ms,
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": data,
-        "config": {
-            "workload": workload, "config": args.workload,
-            "plan": plan, "R_total": nR_tot, "S_total": nS_tot, "R_per_gpu": nR_tot // world,
-            "S_per_gpu": nS_tot // world, "num_buckets": nb, "num_dv_Sa": dv,
-            "emit_pairs": emit, "parallelism": f"bucket-range partition x{world}" if sharded else "single GPU",
-            "exchange_chunks": (C if sharded else None),
-            "exchange_partitioner": ((("single-pass hj3d_partition_strided" if args.xpart == "single" else
-                                       "stable two-pass hj3d_partition") + " (probe side); stable (build side)")
-                                     if sharded else None),
-            "exchange": ("libhj3d hj3d_comm_* over RCCL" if sharded and not args.rehearse else
-                         "torch.distributed gloo, host-staged (rehearsal)" if sharded else None),
-            "rehearsal_one_gpu": bool(args.rehearse),
-            # the packed probe's LDS-slice geometry on this rank: P slices of W buckets; C > 1 = two
-            # partition levels (k_pk_part into P1 ranges of C slices, k_pk_split by slice)
-            "probe_slices": ctx.pk_plan(max(nb // world, 1), max(nB, 1)) if packed else None,
-        },
-        "build_ms": build_ms,
-        "probe_ms": probe_ms,
-        "join_tuples_per_s": nS_tot / ((build_ms + probe_ms) * 1e-3),
-        "input_generation_s": gen_s,
+        **headline(build_ms, probe_ms, wall_ms),
         "roofline": {
             **roof,
             "kernels": kernels,
@@ -843,9 +922,6 @@ def main():
         pp["frac_of_copy_peak"] = pp["achieved_GBs"] / line["roofline"]["copy_peak_GBs"]
     if world > 1:
         line["per_gpu"] = per_gpu
-    if sharded:
-        line["config"]["probe_send_pairs"] = sum(int(t.shape[0]) for t in sendP_c) if single else nP
-        line["config"]["probe_spilled_chunks"] = sorted(spill)
     line["cpu_baseline"] = None
     if world == 1 and not args.no_cpu_baseline and plan == "Csr":
         m = min(args.cpu_sample, nS)
@@ -1003,6 +1079,46 @@ def main_single_config(args):
     probe_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / args.steps
     timed_launches = launches[-1] if launches else (None, None)
 
+    # the last timed step's result: its counters (and config C's unnested output count, the numerator
+    # of that line's value)
+    arrays = {}
+    if args.workload == "C":
+        r = ctx.probe_result()
+        metric, unit, value = ("unnested output tuples/s (probe + unnest phase), config C", "output tuples/s",
+                               r.n_out / (probe_ms * 1e-3))
+        workload = (f"config C: exp1 plan Nrs (3D table on S.a, probe R, unnest), |R|={nR} |S|={nS}, "
+                    f"S.a ~ Zipf({args.theta})")
+        data = ("the reference's generator (hj3d_gen_exp1_ref = Experiment1::init with zipf_distribution, "
+                f"theta={args.theta}, bit-exact)")
+        if args.dump_outputs:
+            arrays["counters"] = np.array([r.n_probe, r.n_matched, r.n_out, r.n_cmps], dtype=np.float64)
+            arrays["out_pairs"] = sample_pairs(torch, out, min(r.n_out, out.shape[0]))
+    else:
+        metric, unit, value = ("probe tuples/s (R through both 3D probes + deferred unnest), config E",
+                               "probe tuples/s", nR / (probe_ms * 1e-3))
+        workload = (f"config E: exp4 plan Ndu (two 3D probes, deferred unnesting), log2R={log2R} alpha=3 A=4 beta=2 "
+                    f"B=2, |S|=|T|={S.shape[0]}")
+        data = "the reference's generator (hj3d_gen_exp4_ref = Experiment4::init, bit-exact)"
+        if args.dump_outputs:
+            r = ctx.probe2_result()  # (the strand materialises nothing: its counters and row sums are its result)
+            keys = ("c_probe_rs", "c_probe_rs_cmp", "c_probe_rt", "c_probe_rt_cmp", "c_unnest_1", "c_unnest_2", "c_top",
+                    "sum_a", "sum_b", "sum_c")
+            arrays["counters"] = np.array([r[k] for k in keys], dtype=np.float64)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, arrays)
+    head = {
+        "metric": metric, "value": value, "unit": unit, "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": wall_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
+        "data": data, "config": {"workload": workload, "config": args.workload, "parallelism": "single GPU"},
+        "build_ms": build_ms, "probe_ms": probe_ms,
+        "launches_per_step": {"build": timed_launches[0], "probe": timed_launches[1],
+                              "note": "kernel launches of libhj3d per timed step (hj3d_launch_count)"},
+    }
+    if not args.full:
+        _emit(head, args)
+        return
+
+    # ---- --full: verification step, roofline, copy peak, CPU baseline ----
     verify = {}
     if args.workload == "C":
         state["ck"] = True
@@ -1026,12 +1142,6 @@ def main_single_config(args):
         n_out = r.n_out
         # phase bytes: build 20 B/tuple; probe 20 B/probe + unnest 12 B/output
         build_bytes, probe_bytes = nS * 20, nR * 20 + n_out * 12
-        workload = (f"config C: exp1 plan Nrs (3D table on S.a, probe R, unnest), |R|={nR} |S|={nS}, "
-                    f"S.a ~ Zipf({args.theta})")
-        data = ("the reference's generator (hj3d_gen_exp1_ref = Experiment1::init with zipf_distribution, "
-                f"theta={args.theta}, bit-exact)")
-        metric, unit, value = ("unnested output tuples/s (probe + unnest phase), config C", "output tuples/s",
-                               n_out / (probe_ms * 1e-3))
         n_build = nS
     else:
         state["ck"] = True  # verification step: the same step with the triple checksums folded in
@@ -1058,19 +1168,9 @@ def main_single_config(args):
         n_build = S.shape[0] + T.shape[0]
         build_bytes = n_build * 16  # 8-B {k,a} tuple read + 8 B (key,row) written
         probe_bytes = nR * 8 * 2 + n_out * 12
-        workload = (f"config E: exp4 plan Ndu (two 3D probes, deferred unnesting), log2R={log2R} alpha=3 A=4 beta=2 "
-                    f"B=2, |S|=|T|={S.shape[0]}")
-        data = "the reference's generator (hj3d_gen_exp4_ref = Experiment4::init, bit-exact)"
-        metric, unit, value = ("probe tuples/s (R through both 3D probes + deferred unnest), config E",
-                               "probe tuples/s", nR / (probe_ms * 1e-3))
     verified = all(v for k, v in verify.items() if k != "against")
     line = {
-        "metric": metric, "value": value, "unit": unit, "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": wall_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
-        "data": data, "config": {"workload": workload, "config": args.workload, "parallelism": "single GPU"},
-        "build_ms": build_ms, "probe_ms": probe_ms,
-        "launches_per_step": {"build": timed_launches[0], "probe": timed_launches[1],
-                              "note": "kernel launches of libhj3d per timed step (hj3d_launch_count)"},
+        **head,
         "roofline": {"bound": "hbm", "kernel": "phase (build / probe)", "unit": "GB/s", "peak": PEAK_HBM_GBS,
                      "achieved": probe_bytes / (probe_ms * 1e-3) / 1e9,
                      "frac": probe_bytes / (probe_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, "traffic": None,

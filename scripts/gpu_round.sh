@@ -15,6 +15,8 @@ export TMPDIR=/tmp
 TAG=${TAG:-r04}
 PART=${PART:-tb}
 mkdir -p gpurun_out/prof
+LOGS=${LOGS:-bench_logs}  # the --full bench lines of parts b, c and d are logged here
+mkdir -p "$LOGS"
 step() { echo "[$(date +%T)] $*"; }
 prof() {  # name, bench args...: rocprofv3 kernel stats of a short bench run
   local name=$1; shift
@@ -43,8 +45,8 @@ if [[ $PART == *b* ]]; then
   bash scripts/gpu_pmc.sh ${TAG} || exit 1
   python scripts/pmc_summary.py ${TAG} --out gpurun_out/${TAG}_pmc.json && cp gpurun_out/${TAG}_pmc.json profiles/ || exit 1
   step bench B
-  timeout -k 10 600 python bench.py > gpurun_out/${TAG}_bench.log 2>&1 || { tail -20 gpurun_out/${TAG}_bench.log; exit 1; }
-  tail -1 gpurun_out/${TAG}_bench.log | cut -c1-400
+  timeout -k 10 600 python bench.py --full > $LOGS/${TAG}_bench.log 2>&1 || { tail -20 $LOGS/${TAG}_bench.log; exit 1; }
+  tail -1 $LOGS/${TAG}_bench.log | cut -c1-400
 fi
 if [[ $PART == *c* ]]; then
   for w in C E; do
@@ -54,15 +56,15 @@ if [[ $PART == *c* ]]; then
     python scripts/pmc_summary.py ${TAG}_$w --workload $w --out gpurun_out/${TAG}_${w}_pmc.json &&
       cp gpurun_out/${TAG}_${w}_pmc.json profiles/ || exit 1
     step bench $w
-    timeout -k 10 600 python bench.py --workload $w --steps 10 --warmup 2 > gpurun_out/${TAG}_$w.log 2>&1 || { tail -20 gpurun_out/${TAG}_$w.log; exit 1; }
-    tail -1 gpurun_out/${TAG}_$w.log | cut -c1-300
+    timeout -k 10 600 python bench.py --full --workload $w --steps 10 --warmup 2 > $LOGS/${TAG}_$w.log 2>&1 || { tail -20 $LOGS/${TAG}_$w.log; exit 1; }
+    tail -1 $LOGS/${TAG}_$w.log | cut -c1-300
   done
 fi
 if [[ $PART == *d* ]]; then
   for plan in Csr Nrs; do
     step bench D $plan
-    timeout -k 10 900 python bench.py --workload D --plan $plan --steps 5 --warmup 1 > gpurun_out/${TAG}_D_$plan.log 2>&1 || { tail -20 gpurun_out/${TAG}_D_$plan.log; exit 1; }
-    tail -1 gpurun_out/${TAG}_D_$plan.log | cut -c1-300
+    timeout -k 10 900 python bench.py --full --workload D --plan $plan --steps 5 --warmup 1 > $LOGS/${TAG}_D_$plan.log 2>&1 || { tail -20 $LOGS/${TAG}_D_$plan.log; exit 1; }
+    tail -1 $LOGS/${TAG}_D_$plan.log | cut -c1-300
     prof ${TAG}_D_$plan --workload D --plan $plan --steps 3 --warmup 1
   done
 fi

@@ -23,6 +23,15 @@ def _bin(name):
     return os.path.join(REF_DIR, name)
 
 
+def _env():
+    """The drop-in binaries find libhj3d.so through an rpath relative to themselves; where
+    oracle/_ref/ is a link to a directory outside the tree that path leads nowhere, so the tests
+    also name the tree's library directory to the loader."""
+    lib = os.path.join(ROOT, "3d-hashjoin_amd", "lib")
+    old = os.environ.get("LD_LIBRARY_PATH")
+    return dict(os.environ, LD_LIBRARY_PATH=lib + (os.pathsep + old if old else ""))
+
+
 def _have(*names):
     return all(os.path.exists(_bin(n)) for n in names)
 
@@ -48,7 +57,7 @@ def _cpu_only():
 def test_dropin_fails_loudly_without_gpu(tmp_path):
     r = subprocess.run([_bin("dropin_main_experiment1.out"), "-R", "6", "-S", "8", "--no-skew", "-t", "0",
                         "--measure-file", str(tmp_path / "m.csv"), "-p", "Csr"],
-                       capture_output=True, text=True, timeout=120)
+                       capture_output=True, text=True, timeout=120, env=_env())
     assert r.returncode != 0
     assert "no CPU path" in r.stderr
 
@@ -65,7 +74,7 @@ def _run_pair(tmp_path, exe, args):
         m = tmp_path / f"{tag}.csv"
         name = exe if tag == "ref" else "dropin_" + exe
         r = subprocess.run([_bin(name)] + args + ["--measure-file", str(m)], capture_output=True, text=True,
-                           timeout=600, cwd=str(tmp_path))
+                           timeout=600, cwd=str(tmp_path), env=_env())
         assert r.returncode == 0, f"{name}: {r.stderr[-2000:]}"
         out[tag] = _rows(m)
     return out["ref"], out["dropin"]

@@ -30,7 +30,7 @@ def test_two_rank_partitioned_join_equals_reference(plan, tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--rehearse", "--workload", "D", "--nR", "1048576", "--nS", "8388608", "--plan", plan,
-           "--steps", "2", "--warmup", "1", "--chunks", "3", "--json-out", str(out)]
+           "--steps", "2", "--warmup", "1", "--chunks", "3", "--full", "--json-out", str(out)]
     env = dict(os.environ, OMP_NUM_THREADS="4")
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=110, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
@@ -212,7 +212,7 @@ def test_bench_dist_path_on_rccl_equals_reference(plan, tmp_path):
     out = tmp_path / "line.json"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist-path", "--workload", "D",
            "--nR", "1048576", "--nS", "8388608", "--plan", plan, "--steps", "2", "--warmup", "1", "--chunks", "3",
-           "--json-out", str(out), "--no-cpu-baseline"]
+           "--full", "--json-out", str(out), "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = json.loads(out.read_text())
