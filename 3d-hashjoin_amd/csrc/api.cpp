@@ -747,7 +747,9 @@ hj3d_status hj3d_probe2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* t
   if (!ctx || !ts || !tt) return HJ3D_EINVAL;
   if (!rel_ok(probe)) return fail(ctx, HJ3D_EINVAL, "hj3d_probe2: invalid relation");
   if (ts->desc.kind != tt->desc.kind) return fail(ctx, HJ3D_EINVAL, "hj3d_probe2: both tables must be of one kind");
-  if (flags & HJ3D_PROBE_EMIT) return fail(ctx, HJ3D_EUNSUPPORTED, "hj3d_probe2: triple materialisation not implemented");
+  if ((flags & HJ3D_PROBE_EMIT) && !out_dev && out_cap) return fail(ctx, HJ3D_EINVAL, "hj3d_probe2: EMIT without buffer");
+  if ((flags & HJ3D_PROBE_EMIT) && (flags & HJ3D_PROBE_ACCUMULATE))
+    return fail(ctx, HJ3D_EINVAL, "hj3d_probe2: EMIT with ACCUMULATE (the strand has no accumulate form)");
   if (hipError_t re = resolve(ctx, ts); re != hipSuccess) return from_hip(ctx, re, "hj3d_probe2");
   if (hipError_t re = resolve(ctx, tt); re != hipSuccess) return from_hip(ctx, re, "hj3d_probe2");
   PhaseTimer tm(ctx, HJ3D_T_PROBE);
@@ -757,6 +759,9 @@ hj3d_status hj3d_probe2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* t
     PhaseTimer tk(ctx, HJ3D_T_PROBE_KERNEL);
     e = probe2(ctx, ts, tt, *probe, flags, out_dev, out_cap, res, ctx->stream);  // (clears res itself)
   }
+  // remember what the overflow check needs (hj3d_probe2_result)
+  ctx->res2_flags = flags;
+  ctx->res2_cap = (flags & HJ3D_PROBE_EMIT) ? out_cap : ~0ull;
   return from_hip(ctx, e, "hj3d_probe2");
 }
 
@@ -770,6 +775,9 @@ hj3d_status hj3d_probe2_result(hj3d_ctx* ctx, hj3d_probe2_res* out) {
   if (const hj3d_status gs = gbar_check(ctx, gw); gs != HJ3D_OK) return gs;
   static_assert(sizeof(hj3d_probe2_res) == 12 * sizeof(uint64_t), "probe2 result layout");
   std::memcpy(out, h, sizeof(hj3d_probe2_res));
+  // c_top counts every triple; those past the buffer were dropped
+  if ((ctx->res2_flags & HJ3D_PROBE_EMIT) && out->c_top > ctx->res2_cap)
+    return fail(ctx, HJ3D_EOVERFLOW, "hj3d_probe2: output buffer too small");
   return HJ3D_OK;
 }
 

@@ -84,6 +84,8 @@ struct hj3d_ctx {
   uint64_t res_nprobe = 0;    // probe tuples of the last probe (strand, when accumulating)
   bool res_overflow = false;  // a dense-output probe of the strand had fewer slots than tuples
   bool res_accumulated = false;
+  uint32_t res2_flags = 0;    // flags and output capacity of the last hj3d_probe2 (overflow check in
+  uint64_t res2_cap = ~0ull;  // hj3d_probe2_result)
   // phase timers
   int timing = 0;  // hj3d_ctx_timing: 0 off, 1 every timer, 2 dispatch-carried kernel spans only
   bool force_direct = false;  // HJ3D_OPT_FORCE_DIRECT: never use the radix-partitioned paths

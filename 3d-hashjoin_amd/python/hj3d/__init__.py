@@ -191,6 +191,32 @@ def pair_hash(a: int, b: int) -> int:
     return mix64(((a & 0xFFFFFFFF) << 32) | (b & 0xFFFFFFFF))
 
 
+def triple_hash(a: int, b: int, c: int) -> int:
+    return mix64(pair_hash(a, b) ^ (c & 0xFFFFFFFF))
+
+
+def triple_checksums(triples) -> dict:
+    """Order-independent checksums of (r, s, t) row triples ((n, 3) integer array; the rows are taken
+    mod 2^32) as hj3d_probe2 folds them: {n, sum_a, sum_b, sum_c, sum_h, xor_h}, sums mod 2^64.
+    Host only (numpy)."""
+    import numpy as np
+    t = np.asarray(triples)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("triples must be an (n, 3) array")
+    u = t.astype(np.int64, copy=False).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    a, b, c = u[:, 0], u[:, 1], u[:, 2]
+
+    def mix(z):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
+        return z ^ (z >> np.uint64(31))
+    with np.errstate(over="ignore"):
+        h = mix(mix((a << np.uint64(32)) | b) ^ c)
+        return {"n": int(len(u)), "sum_a": int(a.sum(dtype=np.uint64)), "sum_b": int(b.sum(dtype=np.uint64)),
+                "sum_c": int(c.sum(dtype=np.uint64)), "sum_h": int(h.sum(dtype=np.uint64)),
+                "xor_h": int(np.bitwise_xor.reduce(h)) if len(h) else 0}
+
+
 def _torch():
     import torch
     return torch
@@ -352,17 +378,34 @@ class Context:
             self._check(st, "hj3d_probe_result")
         return ProbeResult(*(getattr(r, f) for f, _ in _ProbeRes._fields_), overflow=st == HJ3D_EOVERFLOW)
 
-    def probe2(self, ts: "Table", tt: "Table", rel: Rel, fetch: bool = True, checksum: bool = True) -> Optional[dict]:
+    def probe2(self, ts: "Table", tt: "Table", rel: Rel, fetch: bool = True, checksum: bool = True,
+               out=None) -> Optional[dict]:
         """The experiment-4 strand. checksum=False leaves out the triple hashes (sum_h, xor_h: a
-        verification aid the reference does not compute); counters and row sums stay exact."""
+        verification aid the reference does not compute); counters and row sums stay exact.
+        out: a contiguous (cap, 3) int32 device tensor that receives the output triples
+        (r_row, s_row, t_row), at most cap of them, in no specified order; c_top counts all, and the
+        result's `overflow` tells whether some did not fit."""
         flags = PROBE_CHECKSUM if checksum else 0
-        self._check(lib().hj3d_probe2(self.h, ts.h, tt.h, C.byref(rel.c), flags, None, 0), "hj3d_probe2")
+        ptr, cap = None, 0
+        if out is not None:
+            torch = _torch()
+            if not out.is_cuda or out.dtype not in (torch.int32, torch.uint32) or out.dim() != 2 or \
+                    out.shape[1] != 3 or not out.is_contiguous():
+                raise ValueError("out must be a contiguous (cap, 3) int32 device tensor")
+            flags |= PROBE_EMIT
+            cap = out.shape[0]
+            ptr = out.data_ptr() if cap else None
+        self._check(lib().hj3d_probe2(self.h, ts.h, tt.h, C.byref(rel.c), flags, ptr, cap), "hj3d_probe2")
         return self.probe2_result() if fetch else None
 
     def probe2_result(self) -> dict:
         r = _Probe2Res()
-        self._check(lib().hj3d_probe2_result(self.h, C.byref(r)), "hj3d_probe2_result")
-        return {f: getattr(r, f) for f, _ in _Probe2Res._fields_}
+        st = lib().hj3d_probe2_result(self.h, C.byref(r))
+        if st not in (HJ3D_OK, HJ3D_EOVERFLOW):
+            self._check(st, "hj3d_probe2_result")
+        d = {f: getattr(r, f) for f, _ in _Probe2Res._fields_}
+        d["overflow"] = st == HJ3D_EOVERFLOW
+        return d
 
     # ---- selection pushdown (AlgSelection / AlgDynSelection, algebra.hh:278-358) ----
     def select(self, rel: Rel, preds, out_pairs=None, count=None, fetch: bool = True):

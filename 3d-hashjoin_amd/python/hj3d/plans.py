@@ -226,10 +226,12 @@ def exp4_relations_ref(log2R: int, alpha: int, mult_a: int, beta: int, mult_b: i
     return R, S, T
 
 
-def exp4_plan(ctx: Context, plan: str, R, S, T, nb: int, fused: bool = True) -> dict:
+def exp4_plan(ctx: Context, plan: str, R, S, T, nb: int, fused: bool = True, out=None,
+              checksum: bool = True) -> dict:
     """Experiment-4 Ndu (nested, deferred unnesting) or Chj (chaining) on {k,a} relations. fused:
     both tables built by one hj3d_build_many call (one launch sequence for two nested tables),
-    else one hj3d_build each (main_experiment4.cc:879-881)."""
+    else one hj3d_build each (main_experiment4.cc:879-881). out: a (cap, 3) int32 device tensor for
+    the output triples (Context.probe2)."""
     kind = HJ3D_NESTED if plan == "Ndu" else HJ3D_CHAIN
     ts, tt = Table(ctx, kind, nb), Table(ctx, kind, nb)
     rs, rt = Rel(S, key_word=1), Rel(T, key_word=1)
@@ -238,7 +240,7 @@ def exp4_plan(ctx: Context, plan: str, R, S, T, nb: int, fused: bool = True) -> 
     else:
         ts.build(rs)
         tt.build(rt)
-    r = ctx.probe2(ts, tt, Rel(R, key_word=0))
+    r = ctx.probe2(ts, tt, Rel(R, key_word=0), out=out, checksum=checksum)
     return r
 
 
@@ -249,18 +251,19 @@ EXP4_SUM = ("c_probe_rs", "c_probe_rs_cmp", "c_probe_rt", "c_probe_rt_cmp", "c_u
 def merge_exp4(parts: list) -> dict:
     """Experiment-4 counters of disjoint bucket ranges (probe2 results): every counter and row sum
     adds (each R tuple, and every S / T tuple it can meet, lives in exactly one range), the triple
-    hash xor-folds."""
+    hash xor-folds; overflow if any range's triples did not fit its output."""
     from . import MASK64
     out = {k: sum(r[k] for r in parts) & MASK64 for k in EXP4_SUM}
     x = 0
     for r in parts:
         x ^= r["xor_h"]
     out["xor_h"] = x
+    out["overflow"] = any(r.get("overflow", False) for r in parts)
     return out
 
 
 def exp4_plan_sharded(ctx: Context, plan: str, R, S, T, nb: int, parts: int, timing: list | None = None,
-                      checksum: bool = True) -> dict:
+                      checksum: bool = True, out=None) -> dict:
     """Experiment 4 split as the multi-GPU strand splits it (Ndu co-partitions R, S and T
     on the one FK hash, one exchange), emulated on ONE device owner after owner: R (on R.k), S and T
     (on S.a, T.a) are partitioned into `parts` bucket ranges by the exchange partitioner
@@ -268,7 +271,10 @@ def exp4_plan_sharded(ctx: Context, plan: str, R, S, T, nb: int, parts: int, tim
     chain order); owner p builds its S and T tables over [lo, hi) from its pairs (explicit global rows,
     one hj3d_build_many for both) and runs the two-table probe strand with its R pairs (hj3d_probe2:
     main_experiment4.cc:831-941 Ndu, 943-1043 Chj). The owners' counters add up to the single-device
-    run's (merge_exp4). timing: per-owner build / probe ms appended (library timers)."""
+    run's (merge_exp4). timing: per-owner build / probe ms appended (library timers).
+    out: a (cap, 3) int32 device tensor for the output triples; owner p writes its triples behind the
+    previous owners' (at out[sum of their c_top:]). The rows are global, so the owners' triples
+    together are the single-table run's."""
     import torch
     from . import T_BUILD, T_PARTITION, T_PROBE, part_range
     kind = HJ3D_NESTED if plan == "Ndu" else HJ3D_CHAIN
@@ -295,6 +301,7 @@ def exp4_plan_sharded(ctx: Context, plan: str, R, S, T, nb: int, parts: int, tim
     if timing is not None:
         timing.append(dict(owner="partition", **timers()))
     res = []
+    ooff = 0  # triples of the owners so far
     for p in range(parts):
         lo, hi = part_range(nb, parts, p)
         ts, tt = Table(ctx, kind, nb, lo, hi), Table(ctx, kind, nb, lo, hi)
@@ -302,7 +309,9 @@ def exp4_plan_sharded(ctx: Context, plan: str, R, S, T, nb: int, parts: int, tim
         ts.reserve(max(own[1].n, 1))
         tt.reserve(max(own[2].n, 1))
         ctx.build_many([ts, tt], [own[1], own[2]])
-        res.append(ctx.probe2(ts, tt, own[0], checksum=checksum))
+        res.append(ctx.probe2(ts, tt, own[0], checksum=checksum,
+                              out=out[min(ooff, out.shape[0]):] if out is not None else None))
+        ooff += res[-1]["c_top"]
         if timing is not None:
             timing.append(dict(owner=p, bucket_lo=lo, bucket_hi=hi, probe_tuples=own[0].n, build_tuples=own[1].n + own[2].n,
                                **timers()))

@@ -317,9 +317,17 @@ hj3d_status hj3d_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* probe
 hj3d_status hj3d_probe_result(hj3d_ctx* ctx, hj3d_probe_res* out);
 
 /* Experiment-4 probe strand over two tables built on S and T (both HJ3D_NESTED: Ndu with deferred
- * unnesting; both HJ3D_CHAIN: Chj). With HJ3D_PROBE_EMIT, triples {u32 r, s, t} go to out_dev.
+ * unnesting; both HJ3D_CHAIN: Chj). With HJ3D_PROBE_EMIT, the output triples go to out_dev as an array
+ * of {u32 r_row, u32 s_row, u32 t_row} (12 bytes each, out_dev 4-byte aligned), at most out_cap of
+ * them, in no specified order (it differs from run to run); nothing is written at or beyond
+ * out_dev + 12 * out_cap. c_top and every other counter and checksum still count all triples, and
+ * hj3d_probe2_result returns HJ3D_EOVERFLOW (with the complete counters) if c_top > out_cap; the
+ * out_cap triples written are then some out_cap of the result. EMIT with out_dev == NULL and
+ * out_cap > 0, and EMIT with HJ3D_PROBE_ACCUMULATE (the strand has no accumulate form; without EMIT
+ * that flag is ignored), are HJ3D_EINVAL. Replaces the two unnest functors of
+ * main_experiment4.cc:435-466 filling result_tuple_t.
  * The row sums sum_a / sum_b / sum_c are always folded (the unnest reads every output triple's
- * rows); the triple hashes sum_h / xor_h only with HJ3D_PROBE_CHECKSUM (else 0). */
+ * rows); the triple hashes sum_h / xor_h only with HJ3D_PROBE_CHECKSUM (else 0), with or without EMIT. */
 hj3d_status hj3d_probe2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const hj3d_rel* probe,
                         uint32_t flags, void* out_dev, uint64_t out_cap);
 hj3d_status hj3d_probe2_result(hj3d_ctx* ctx, hj3d_probe2_res* out);
