@@ -410,7 +410,10 @@ hj3d_status hj3d_build_many(hj3d_ctx* ctx, hj3d_table* const* tables, const hj3d
     const char* path = "nested_agg";
     {
       PhaseTimer tm(ctx, HJ3D_T_BUILD);
-      for (uint32_t k = 0; k < 2; ++k) tables[k]->pending = false;
+      for (uint32_t k = 0; k < 2; ++k) {
+        tables[k]->pending = false;
+        tables[k]->gbar_tag = 0;  // (as build_one: no nested build records a barrier tag)
+      }
       e = nested_host_counts(tables[0]);
       if (e == hipSuccess) e = nested_host_counts(tables[1]);
       if (e == hipSuccess) e = nested_build_agg_many(ctx, tables, builds, 2, ctx->stream, &path);
@@ -528,6 +531,7 @@ hipError_t table_resolve(hj3d_ctx* ctx, hj3d_table* t) {
     // the rest of the build: timed as build work (not inside the probe that triggered it)
     PhaseTimer tm(ctx, HJ3D_T_BUILD);
     t->path = "nested_sort";
+    t->gbar_tag = 0;  // the content is replaced: counts word 3 becomes the sort build's largest key
     e = nested_build(ctx, t, t->pending_rel, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(hc, t->counts.p, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);

@@ -159,7 +159,10 @@ struct hj3d_table {
   hj3d::DevBuf off, ent, main, sub;
   hj3d::DevBuf counts;    // device u64[4]: {entries, distinct, max_sub_len, give-up flag (nested) /
                           // fused-partition barrier timeout tag (chaining)}
-  uint64_t gbar_tag = 0;  // chaining tables built by the fused partition: its launch tag (0: none)
+  // chaining tables built by the fused partition: its launch tag (0: none). Never set on a nested
+  // table (partition_pairs takes the fused form for HJ3D_CHAIN only), and cleared wherever a table's
+  // content is replaced: build_one, hj3d_build_many, hj3d_table_clear, table_resolve's sort fallback
+  uint64_t gbar_tag = 0;
 };
 
 namespace hj3d {

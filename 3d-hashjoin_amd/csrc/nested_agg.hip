@@ -1565,7 +1565,12 @@ hipError_t nested_build_agg_many(hj3d_ctx* ctx, hj3d_table* const* tt, const hj3
   // the small form's table: ~1.5 slots per bucket, which leaves its pass-B image room for a config-D
   // slice's rows (15.4 K pairs; 2.5 slots per bucket left 11.6 K: D shape 17.7 -> 16.6 ms)
   const uint32_t cap512 = prime_at_least(std::max<uint32_t>(2048, uint32_t(kSmallCapF * W) + kSmallBlock + 64));
-  const bool small = cap512 <= 6144 && agg_lds_words(cap512, W, kSmallBlock) * 4 <= kSmallLds;
+  // Not for one-level tables of at most one partition per CU: two workgroups per CU gain nothing
+  // there, and the small table holds only cap512 / 256 ~ 8 distinct keys per bucket before the last
+  // halved round (1024 -> 512 -> 256 buckets) gives up, against ~24 with the 1024-thread form's
+  // table: a 7000-bucket table of 100 K keys (14 per bucket) went to the sort build after the fact.
+  const bool one_per_cu = !pk && PT <= G;
+  const bool small = !one_per_cu && cap512 <= 6144 && agg_lds_words(cap512, W, kSmallBlock) * 4 <= kSmallLds;
   // the 1024-thread form's table (one workgroup per CU: the whole LDS, the image takes what the table leaves)
   // (a smaller table for a larger image measured slower at config C: 1.87 -> 1.90 ms at 1.2 slots per bucket)
   const uint32_t cap1024 = kAggCapMax;

@@ -219,7 +219,8 @@ __global__ __launch_bounds__(kPBlock) void k_rp_scatter(RelTiles rt, FastMod fm,
 // checks the occupancy); the barrier is a monotonic arrival counter (target = the running sum of
 // the grids launched on it), so it is never reset. A barrier that does not complete in ~0.2 s sets
 // the timeout word and lets the workgroup go on (results wrong, flagged) instead of hanging.
-// Phase 2 stages kFzGroup tiles per pass. One relation only (hj3d_build; hj3d_build_many's two
+// Phase 2 stages kFzGroup tiles per pass. Chaining tables only (a nested table uses the flag word
+// below for its own build). One relation only (hj3d_build; hj3d_build_many's two
 // relations keep the two launches: at config E, 4 tiles per workgroup, the fused form measured
 // 66.9 against 19.4 + 43.8 us, at config B, 5 tiles, 87.0 against 26.4 + 67.5 us).
 // (Phase 2 with one tile per staging pass: 0.1378 / 0.1386 against 0.1344 / 0.1346 ms build at
@@ -1451,10 +1452,14 @@ hipError_t partition_pairs(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r
   rt.tsz = tsz;
   const uint32_t lo = uint32_t(t->desc.bucket_lo);
   // small implicit-row inputs: one fused launch (k_rp_fused) when every workgroup's tiles fit its
-  // registers and the G workgroups are co-resident (the grid barrier needs all of them at once)
+  // registers and the G workgroups are co-resident (the grid barrier needs all of them at once).
+  // Chaining tables only: the barrier's timeout tag goes to word 3 of the table's counts, which on a
+  // nested table is the aggregation build's give-up flag (and later the sort build's largest key),
+  // and k_nagg_order zeroes the counts after the partition, so a timeout there would be lost.
   const bool implicit = r.row_off == HJ3D_ROW_IMPLICIT && (!r1 || r1->row_off == HJ3D_ROW_IMPLICIT);
   const uint32_t tpw = (ntiles + g - 1) / g;
-  if (!ctx->rp_unfused && !r1 && !ws && rounds == uint32_t(kFzRounds) && implicit && tpw <= uint32_t(kFzTMax) &&
+  if (!ctx->rp_unfused && t->desc.kind == HJ3D_CHAIN && !r1 && !ws && rounds == uint32_t(kFzRounds) && implicit &&
+      tpw <= uint32_t(kFzTMax) &&
       t->desc.num_buckets >= 2 && t->desc.num_buckets < (1ull << 32) && pl.W >= 2) {
     const void* kf = tpw <= 2   ? reinterpret_cast<const void*>(&k_rp_fused<2>)
                      : tpw == 3 ? reinterpret_cast<const void*>(&k_rp_fused<3>)

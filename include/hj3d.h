@@ -193,9 +193,11 @@ enum {
    * Default: the table finishes at its next use (see hj3d_build). */
   HJ3D_OPT_SYNC_BUILD = 13,
   /* 14: retired (the two-level nested partition, measured slower than the one-level one) */
-  /* HJ3D_OPT_RP_UNFUSED (0/1, default 0): small implicit-row build partitions run as two launches
-   * (histogram, then scatter) instead of the fused one-launch partition with its grid barrier
-   * (A/B measurements and the parity test of both forms). The fused form runs only when the
+  /* HJ3D_OPT_RP_UNFUSED (0/1, default 0): small implicit-row partitions of chaining builds run as
+   * two launches (histogram, then scatter) instead of the fused one-launch partition with its grid
+   * barrier (A/B measurements and the parity test of both forms). Nested builds always take the two
+   * launches: the barrier's timeout flag lives in a word of the table that a nested table uses for
+   * its own build. The fused form runs only when the
    * occupancy API confirms all its workgroups are resident (another stream holding CUs can still
    * delay some); should a barrier not complete within 0.2 s, its workgroups go on with partial
    * partition sizes and the table is invalid: hj3d_table_stats / _size / _export / _finish of that
@@ -204,7 +206,8 @@ enum {
   HJ3D_OPT_RP_UNFUSED = 15,
   /* HJ3D_OPT_DIAG_GBAR (ticks of the 100 MHz clock, default 0 = off): diagnostic for the failure path
    * above. The fused partition's barrier then times out after this many ticks, and its workgroup 0
-   * never arrives, so every barrier of such a build times out (tests). */
+   * never arrives, so every barrier of such a build times out (tests). Chaining builds only: no
+   * nested build takes the fused partition. */
   HJ3D_OPT_DIAG_GBAR = 16,
   /* HJ3D_OPT_DIAG_LOOKBACK (ticks of the 100 MHz clock, default 0 = off): diagnostic of the nested
    * build on the packed slices (the aggregation form that finishes by decoupled look-back: each
