@@ -364,6 +364,11 @@ hj3d_status hj3d_table_clear(hj3d_ctx* ctx, hj3d_table* t) {
   if (e == hipSuccess) e = hipMemsetAsync(t->counts.p, 0, 4 * sizeof(uint64_t), ctx->stream);
   t->n_build = 0;
   t->n_mains = 0;
+  // no build made the (empty) content: the state of a table never built. Probes find every bucket
+  // empty in `off` and read nothing else; the packed probe (which wants a built table) leaves an
+  // unbuilt one to the partitioned or the direct probe.
+  t->built = false;
+  t->path = "none";
   return from_hip(ctx, e, "hj3d_table_clear");
 }
 

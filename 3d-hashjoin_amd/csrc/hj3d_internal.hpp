@@ -155,7 +155,11 @@ struct hj3d_table {
   hipEvent_t hc_ev = nullptr;
   // chaining: off[nb_local+1] (u32 CSR offsets), ent[n] = {hash, row}
   // nested:   off[nb_local+1] over mains, main[d] = {hash, first_row, sub_off, sub_len},
-  //           sub[n] = build rows grouped per key (first occurrence first, then row order)
+  //           sub[n] = build rows grouped per key, a key's rows in sub[sub_off .. + sub_len) in no
+  //           defined order (the sort build leaves them ascending for implicit rows; the aggregation
+  //           builds place them by atomics, k_nagg_hot writes a hot key's rows down from the end of
+  //           its partition's range); n = the build relation's tuples, of which a bucket-range shard's
+  //           ranges cover only the stored ones (hj3d.h, hj3d_table_export)
   hj3d::DevBuf off, ent, main, sub;
   hj3d::DevBuf counts;    // device u64[4]: {entries, distinct, max_sub_len, give-up flag (nested) /
                           // fused-partition barrier timeout tag (chaining)}

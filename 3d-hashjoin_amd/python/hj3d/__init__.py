@@ -767,6 +767,7 @@ class Table:
         self.h = h
         self.kind = kind
         self.num_buckets = num_buckets
+        self.bucket_lo, self.bucket_hi = desc.bucket_lo, desc.bucket_hi
 
     def reserve(self, n: int):
         self.ctx._check(lib().hj3d_table_reserve(self.ctx.h, self.h, n), "hj3d_table_reserve")
@@ -792,6 +793,32 @@ class Table:
         s = _Stats()
         self.ctx._check(lib().hj3d_table_stats(self.ctx.h, self.h, C.byref(s)), "hj3d_table_stats")
         return {f: getattr(s, f) for f, _ in _Stats._fields_}
+
+    def size(self):
+        """(n_entries, n_distinct): tuples / distinct keys currently stored (hj3d_table_size)."""
+        ne, nd = C.c_uint64(), C.c_uint64()
+        self.ctx._check(lib().hj3d_table_size(self.ctx.h, self.h, C.byref(ne), C.byref(nd)), "hj3d_table_size")
+        return ne.value, nd.value
+
+    def export(self):
+        """Host copy of the table's arrays (hj3d_table_export, its two calls: sizes, then contents) as
+        numpy u32 arrays (off, payload, sub): off[nb_local + 1]; payload (n, 2) = chaining entries
+        {hash, row} or (n, 4) = nested main records {hash, first_row, sub_off, sub_len}; sub = the
+        nested table's row array (empty for chaining), of which the main records' ranges are parts."""
+        import numpy as np
+        L = lib()
+        npay, nsub = C.c_uint64(), C.c_uint64()
+        self.ctx._check(L.hj3d_table_export(self.ctx.h, self.h, None, None, None, C.byref(npay), C.byref(nsub)),
+                        "hj3d_table_export")
+        nbl = self.bucket_hi - self.bucket_lo
+        off = np.zeros(nbl + 1, dtype=np.uint32)
+        payload = np.zeros((npay.value, 4 if self.kind == HJ3D_NESTED else 2), dtype=np.uint32)
+        sub = np.zeros(nsub.value, dtype=np.uint32)
+        self.ctx._check(L.hj3d_table_export(self.ctx.h, self.h, off.ctypes.data,
+                                            payload.ctypes.data if payload.size else None,
+                                            sub.ctypes.data if sub.size else None, C.byref(npay), C.byref(nsub)),
+                        "hj3d_table_export")
+        return off, payload, sub
 
     def close(self):
         if getattr(self, "h", None):

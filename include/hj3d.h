@@ -265,6 +265,11 @@ hj3d_status hj3d_table_create(hj3d_ctx* ctx, const hj3d_table_desc* desc, hj3d_t
 void        hj3d_table_destroy(hj3d_table* t);
 /* Pre-size device storage for builds of up to max_build tuples (allocation outside timed loops). */
 hj3d_status hj3d_table_reserve(hj3d_ctx* ctx, hj3d_table* t, uint64_t max_build);
+/* Empties the table (asynchronous); its device storage is kept. Afterwards the table is in the state
+ * of one never built: hj3d_table_build_path is "none", every getter succeeds (hj3d_table_export gives
+ * n_payload = n_sub = 0 and all-zero offsets, the statistics are those of an empty table), and probes
+ * are valid and match nothing (n_probe = the probe tuples, every other counter 0; a dense EMIT output
+ * carries 0xFFFFFFFF in every slot). A build in flight for the old content is dropped. */
 hj3d_status hj3d_table_clear(hj3d_ctx* ctx, hj3d_table* t);
 /* Build: replaces the table content with the tuples of `build` (asynchronous). A nested table's
  * build finishes at the table's next use (probe, statistics, export): its counts are read then, and
@@ -282,10 +287,17 @@ hj3d_status hj3d_build_many(hj3d_ctx* ctx, hj3d_table* const* tables, const hj3d
 /* Host copy of a table's device arrays (synchronous): what the drop-in layer's per-tuple probes
  * walk (HtChaining1::findDirEntryByOther ht_chaining.hh:236-248, HtNested1::findMainNodeByOther
  * ht_nested.hh:354-382). Call with NULL arrays first to get the sizes: *n_payload = entries
- * (chaining) or main records (nested), *n_sub = build rows of a nested table (0 for chaining).
+ * (chaining) or main records (nested), *n_sub = the extent of a nested table's row array `sub` (0
+ * for chaining): the tuple count of the build relation, so at least the stored rows.
  * Then off[nb_local + 1] receives the CSR offsets of the local buckets into the payload, payload
  * the chaining entries {u32 hash, u32 row} or the nested main records {u32 hash, first_row,
  * sub_off, sub_len}, and sub (nested) the build rows grouped per key, sub[sub_off .. + sub_len).
+ * The main records' ranges are pairwise disjoint and lie inside [0, n_sub); their lengths add up to
+ * the stored rows (hj3d_stats.entries). For a table that stores every build tuple they tile
+ * [0, n_sub) exactly. A bucket-range shard fed tuples of other buckets leaves n_sub - entries
+ * positions outside every range: the sort build keeps the unowned tuples' rows there, the aggregation
+ * builds pack the stored rows at the front and leave the tail unwritten. No main record refers to
+ * them; a consumer reads sub only through the ranges.
  * Entry order: chaining buckets of <= 32 entries come sorted by row (the reference's chain order is
  * then [first, newest, ..., second], arithmetic in that order); longer buckets are in no defined
  * order (the builds claim their runs with atomics) -- a consumer that needs the reference's chain
@@ -297,7 +309,7 @@ hj3d_status hj3d_table_export(hj3d_ctx* ctx, const hj3d_table* t, uint32_t* off,
  * "slices" (pk_slices, tables beyond the radix build's range) or "direct"; nested "nested_agg",
  * "nested_agg_slices" (more than 2048 partitions), each with "_reg" appended when the register form
  * aggregated them, or "nested_sort"; "none" before a
- * build. A nested table whose build has not been resolved yet (no use since hj3d_build) reports the
+ * build and after hj3d_table_clear. A nested table whose build has not been resolved yet (no use since hj3d_build) reports the
  * path that was started, with "?" appended ("nested_agg?"): the getter never waits or builds. Replaces
  * nothing of the reference (which has one insert path). */
 const char* hj3d_table_build_path(const hj3d_table* t);

@@ -176,9 +176,12 @@ def test_slice_build_equals_reference(pk, name):
 
 @pytest.mark.parametrize("fill", [1.0, 1.3])
 def test_slice_build_large_slices_vs_oracle(pk, fill):
-    """Slices whose fine regions exceed the register-held form (more than 704 pairs, frequent at
-    fill 1.3 with 8192-bucket slices) take the in-kernel HBM path of k_pk_build; random non-unique
-    keys; statistics and both probe forms equal the oracle's."""
+    """The slice build's give-up: random non-unique keys at fill 1.0 and 1.3, one key with ~5 % of the
+    rows. That key overflows the partitioner's regions (~410 of its rows per 8192-tuple tile against a
+    region of 160 pairs), so pk_build hands the table to the direct build; statistics and both probe
+    forms equal the oracle's. (The slice build that keeps such a table, with fine regions beyond the
+    register-held form at fill 1.3, i.e. the in-kernel HBM path of k_pk_build:
+    test_gpu_table_lifecycle.py, `slices` and `slices_fill13`.)"""
     import hj3d
     rng = np.random.default_rng(int(fill * 10))
     nb = 1 << 20
@@ -192,6 +195,7 @@ def test_slice_build_large_slices_vs_oracle(pk, fill):
     try:
         t = hj3d.Table(pk, hj3d.HJ3D_CHAIN, nb)
         t.build(hj3d.Rel(dev(B), 0))
+        assert t.build_path() == "direct", t.build_path()
         st = t.stats()
         for unique in (True, False):
             e = O.chain_plan(B, 0, Pt, 1, nb, unique)
