@@ -627,6 +627,12 @@ static void note_probe(hj3d_ctx* ctx, const hj3d_table* t, uint64_t n, uint32_t 
   ctx->res_accumulated = acc;
 }
 
+// HJ3D_PROBE_MAINREF: the dense slot of a nested probe tuple carries the matched main record's index
+static bool mainref_ok(const hj3d_table* t, uint32_t flags) {
+  return !(flags & HJ3D_PROBE_MAINREF) ||
+         (t->desc.kind == HJ3D_NESTED && (flags & HJ3D_PROBE_EMIT) && !(flags & HJ3D_PROBE_UNNEST));
+}
+
 static bool sel_ok(const hj3d_rel* rel, const hj3d_sel_pred* preds, uint32_t npred) {
   if (npred > HJ3D_SEL_MAX || (npred && !preds)) return false;
   for (uint32_t k = 0; k < npred; ++k)
@@ -641,6 +647,7 @@ hj3d_status hj3d_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* probe
   if ((flags & HJ3D_PROBE_EMIT) && !out_dev && out_cap) return fail(ctx, HJ3D_EINVAL, "hj3d_probe: EMIT without buffer");
   if ((flags & HJ3D_PROBE_UNNEST) && t->desc.kind != HJ3D_NESTED)
     return fail(ctx, HJ3D_EINVAL, "hj3d_probe: UNNEST needs a nested table");
+  if (!mainref_ok(t, flags)) return fail(ctx, HJ3D_EINVAL, "hj3d_probe: MAINREF needs a nested table, EMIT and no UNNEST");
   if (hipError_t re = resolve(ctx, t); re != hipSuccess) return from_hip(ctx, re, "hj3d_probe");
   PhaseTimer tm(ctx, HJ3D_T_PROBE);
   uint64_t* res = ctx->res.as<uint64_t>();
@@ -689,6 +696,8 @@ hj3d_status hj3d_probe_sel(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* p
   if ((flags & HJ3D_PROBE_EMIT) && !out_dev && out_cap) return fail(ctx, HJ3D_EINVAL, "hj3d_probe_sel: EMIT without buffer");
   if ((flags & HJ3D_PROBE_UNNEST) && t->desc.kind != HJ3D_NESTED)
     return fail(ctx, HJ3D_EINVAL, "hj3d_probe_sel: UNNEST needs a nested table");
+  if (!mainref_ok(t, flags))
+    return fail(ctx, HJ3D_EINVAL, "hj3d_probe_sel: MAINREF needs a nested table, EMIT and no UNNEST");
   if (hipError_t re = resolve(ctx, t); re != hipSuccess) return from_hip(ctx, re, "hj3d_probe_sel");
   const bool chain_radix = t->desc.kind == HJ3D_CHAIN && radix_probe_applicable(ctx, t, probe->n);
   const bool nested_radix = t->desc.kind == HJ3D_NESTED && radix_nested_applicable(ctx, t, probe->n);
@@ -788,6 +797,52 @@ hj3d_status hj3d_probe2_result(hj3d_ctx* ctx, hj3d_probe2_res* out) {
   if ((ctx->res2_flags & HJ3D_PROBE_EMIT) && out->c_top > ctx->res2_cap)
     return fail(ctx, HJ3D_EOVERFLOW, "hj3d_probe2: output buffer too small");
   return HJ3D_OK;
+}
+
+hj3d_status hj3d_unnest(hj3d_ctx* ctx, const hj3d_table* t, const void* nested_dev, uint64_t n, uint32_t flags,
+                        void* out_dev, uint64_t out_cap) {
+  if (!ctx || !t) return HJ3D_EINVAL;
+  if (flags & ~(HJ3D_PROBE_EMIT | HJ3D_PROBE_CHECKSUM)) return fail(ctx, HJ3D_EINVAL, "hj3d_unnest: flags other than EMIT, CHECKSUM");
+  if (t->desc.kind != HJ3D_NESTED) return fail(ctx, HJ3D_EINVAL, "hj3d_unnest: needs a nested table");
+  if ((n && !nested_dev) || n >= (1ull << 32)) return fail(ctx, HJ3D_EINVAL, "hj3d_unnest: invalid input");
+  if ((flags & HJ3D_PROBE_EMIT) && !out_dev && out_cap) return fail(ctx, HJ3D_EINVAL, "hj3d_unnest: EMIT without buffer");
+  if (hipError_t re = resolve(ctx, t); re != hipSuccess) return from_hip(ctx, re, "hj3d_unnest");
+  PhaseTimer tm(ctx, HJ3D_T_PROBE);
+  uint64_t* res = ctx->res.as<uint64_t>();
+  hipError_t e = hipMemsetAsync(res, 0, kResFields * sizeof(uint64_t), ctx->stream);
+  if (e == hipSuccess) e = unnest_pairs(ctx, t, nested_dev, n, flags, out_dev, out_cap, res, ctx->stream);
+  // the non-dense overflow convention (out_check): n_out against the capacity, on the stream
+  if (e == hipSuccess && (flags & HJ3D_PROBE_EMIT)) {
+    hipLaunchKernelGGL(k_out_overflow, dim3(1), dim3(64), 0, ctx->stream, res, out_cap);
+    e = hipGetLastError();
+  }
+  ctx->res_flags = flags;
+  ctx->res_dense = false;
+  ctx->res_cap = (flags & HJ3D_PROBE_EMIT) ? out_cap : ~0ull;
+  ctx->res_nprobe = n;
+  ctx->res_overflow = false;
+  ctx->res_accumulated = false;
+  return from_hip(ctx, e, "hj3d_unnest");
+}
+
+hj3d_status hj3d_unnest2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const void* nested_dev,
+                         uint64_t n, uint32_t flags, void* out_dev, uint64_t out_cap) {
+  if (!ctx || !ts || !tt) return HJ3D_EINVAL;
+  if (flags & ~(HJ3D_PROBE_EMIT | HJ3D_PROBE_CHECKSUM)) return fail(ctx, HJ3D_EINVAL, "hj3d_unnest2: flags other than EMIT, CHECKSUM");
+  if (ts->desc.kind != HJ3D_NESTED || tt->desc.kind != HJ3D_NESTED)
+    return fail(ctx, HJ3D_EINVAL, "hj3d_unnest2: needs two nested tables");
+  if ((n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32))
+    return fail(ctx, HJ3D_EINVAL, "hj3d_unnest2: invalid input");
+  if ((flags & HJ3D_PROBE_EMIT) && ((!out_dev && out_cap) || (uintptr_t(out_dev) & 3)))
+    return fail(ctx, HJ3D_EINVAL, "hj3d_unnest2: EMIT without (aligned) buffer");
+  if (hipError_t re = resolve(ctx, ts); re != hipSuccess) return from_hip(ctx, re, "hj3d_unnest2");
+  if (hipError_t re = resolve(ctx, tt); re != hipSuccess) return from_hip(ctx, re, "hj3d_unnest2");
+  PhaseTimer tm(ctx, HJ3D_T_PROBE);
+  const hipError_t e =
+      unnest_triples(ctx, ts, tt, nested_dev, n, flags, out_dev, out_cap, ctx->res.as<uint64_t>(), ctx->stream);
+  ctx->res2_flags = flags;
+  ctx->res2_cap = (flags & HJ3D_PROBE_EMIT) ? out_cap : ~0ull;
+  return from_hip(ctx, e, "hj3d_unnest2");
 }
 
 hj3d_status hj3d_probe_geometry(hj3d_ctx* ctx, uint64_t nb_local, uint64_t n_build, uint32_t out[5]) {

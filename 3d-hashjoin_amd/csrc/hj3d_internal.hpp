@@ -406,6 +406,13 @@ bool radix_nested_applicable(const hj3d_ctx* ctx, const hj3d_table* t, uint64_t 
 hipError_t radix_nested_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, uint32_t flags, void* out,
                               uint64_t out_cap, uint64_t* res_dev, hipStream_t s, const SelArgs* sel = nullptr,
                               const ZeroList* also = nullptr);
+// hj3d_unnest: n stored nested tuples {a, main ref} of t expanded through the materialised unnest's
+// expansion (counters and sums added to res; flags: EMIT, CHECKSUM)
+hipError_t unnest_pairs(hj3d_ctx* ctx, const hj3d_table* t, const void* in, uint64_t n, uint32_t flags, void* out,
+                        uint64_t out_cap, uint64_t* res_dev, hipStream_t s);
+// unnest2.hip: hj3d_unnest2, n triples {a, ref_s, ref_t} expanded to {a, s_row, t_row} (clears res itself)
+hipError_t unnest_triples(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const void* in, uint64_t n,
+                          uint32_t flags, void* out, uint64_t out_cap, uint64_t* res_dev, hipStream_t s);
 // exp4.hip
 hipError_t probe2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const hj3d_rel& r, uint32_t flags,
                   void* out, uint64_t out_cap, uint64_t* res_dev, hipStream_t s);

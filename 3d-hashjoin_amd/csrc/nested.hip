@@ -120,7 +120,9 @@ __global__ __launch_bounds__(kBlock) void k_main_scatter(const uint32_t* __restr
   if ((threadIdx.x & 63) == 0 && wm) atomicMax(reinterpret_cast<unsigned long long*>(counts + 2), wm);
 }
 
-enum NMode { kAggNU = 0, kDenseNU = 1, kAggUN = 2, kCountUN = 3 };
+// kDenseRef (HJ3D_PROBE_MAINREF): kDenseNU whose dense slot carries the matched main record's index
+// instead of its first build row (counters and checksums are kDenseNU's).
+enum NMode { kAggNU = 0, kDenseNU = 1, kAggUN = 2, kCountUN = 3, kDenseRef = 4 };
 
 struct Heavy {
   uint32_t probe_row;
@@ -183,7 +185,7 @@ __global__ __launch_bounds__(kBlock) void k_nested_probe(RelView r, FastMod fm, 
         acc[3] += 1 + before;
         acc[1] += 1;
       }
-      if (MODE == kAggNU || MODE == kDenseNU) {
+      if (MODE == kAggNU || MODE == kDenseNU || MODE == kDenseRef) {
         if (found != kInvalid) {
           acc[2] += 1;
           acc[4] += pr[j];
@@ -193,6 +195,7 @@ __global__ __launch_bounds__(kBlock) void k_nested_probe(RelView r, FastMod fm, 
           acc[8] ^= ph;
         }
         if (MODE == kDenseNU && i < out_cap) out[i] = make_uint2(pr[j], found == kInvalid ? kInvalid : M.y);
+        if (MODE == kDenseRef && i < out_cap) out[i] = make_uint2(pr[j], found);  // kInvalid: no match
       } else if (MODE == kAggUN) {
         if (found != kInvalid) {
           acc[2] += M.w;
@@ -280,7 +283,9 @@ struct SlotSrc {
   }
 };
 
-template <bool SLOTS, bool CK>
+// CK: 0 writes the pairs only; 1 folds the output checksums (row sums and pair hashes); 2 the row sums
+// only (hj3d_unnest without HJ3D_PROBE_CHECKSUM).
+template <bool SLOTS, int CK>
 __global__ __launch_bounds__(kBlock) void k_expand_light(SlotSrc src, uint64_t nslots, const uint64_t* __restrict__ ooff,
                                                          const uint32_t* __restrict__ sub, uint2* __restrict__ out,
                                                          uint64_t out_cap, uint32_t* __restrict__ heavy,
@@ -370,9 +375,11 @@ __global__ __launch_bounds__(kBlock) void k_expand_light(SlotSrc src, uint64_t n
       if (CK && ok[u]) {
         acc[4] += prow;
         acc[5] += br[u];
-        const uint64_t ph = pair_hash(prow, br[u]);
-        acc[7] += ph;
-        acc[8] ^= ph;
+        if (CK == 1) {
+          const uint64_t ph = pair_hash(prow, br[u]);
+          acc[7] += ph;
+          acc[8] ^= ph;
+        }
       }
     }
   }
@@ -426,7 +433,7 @@ __global__ __launch_bounds__(1024) void k_heavy_offsets(const uint32_t* __restri
 // coalesced and a lane binary-searches hoff only once (a heavy slot spans >= kHeavyOut outputs).
 constexpr uint32_t kHeavySpan = 64 * 16;
 
-template <bool SLOTS, bool CK>
+template <bool SLOTS, int CK>
 __global__ __launch_bounds__(kBlock) void k_expand_heavy_flat(SlotSrc src, const uint64_t* __restrict__ ooff,
                                                               const uint32_t* __restrict__ sub,
                                                               const uint32_t* __restrict__ heavy,
@@ -467,9 +474,11 @@ __global__ __launch_bounds__(kBlock) void k_expand_heavy_flat(SlotSrc src, const
       if (CK) {
         acc[4] += pr;
         acc[5] += br;
-        const uint64_t ph = pair_hash(pr, br);
-        acc[7] += ph;
-        acc[8] ^= ph;
+        if (CK == 1) {
+          const uint64_t ph = pair_hash(pr, br);
+          acc[7] += ph;
+          acc[8] ^= ph;
+        }
       }
     }
   }
@@ -507,7 +516,7 @@ __device__ __forceinline__ void nested_bucket(uint32_t h, uint32_t pr, const MT*
     acc[3] += 1 + before;
     acc[1] += 1;
   }
-  if (MODE == kAggNU || MODE == kDenseNU) {
+  if (MODE == kAggNU || MODE == kDenseNU || MODE == kDenseRef) {
     if (found != kInvalid) {
       acc[2] += 1;
       acc[4] += pr;
@@ -517,6 +526,7 @@ __device__ __forceinline__ void nested_bucket(uint32_t h, uint32_t pr, const MT*
       acc[8] ^= ph;
     }
     if (MODE == kDenseNU && i < out_cap) out[i] = make_uint2(pr, found == kInvalid ? kInvalid : F.y);
+    if (MODE == kDenseRef && i < out_cap) out[i] = make_uint2(pr, found == kInvalid ? kInvalid : mg0 + found);
   } else if (MODE == kAggUN) {
     if (found != kInvalid) {
       acc[2] += F.w;
@@ -696,15 +706,17 @@ namespace {
 // Light expansion (one workgroup per 256 slots, partials per workgroup) then the heavy slots
 // flattened over the chip (hoff in kScrD).
 // ck: fold the output checksums (HJ3D_PROBE_CHECKSUM; the light kernel's per-workgroup partials
-// are then reduced by the caller), otherwise the expansion only writes the pairs.
-hipError_t expand(hj3d_ctx* ctx, const SlotSrc& src, bool slots, bool ck, uint64_t nslots, const uint64_t* ooff,
+// are then reduced by the caller), otherwise the expansion only writes the pairs. ck = 2 (slots only:
+// hj3d_unnest without HJ3D_PROBE_CHECKSUM) folds the row sums and leaves the pair hashes out.
+hipError_t expand(hj3d_ctx* ctx, const SlotSrc& src, bool slots, int ck, uint64_t nslots, const uint64_t* ooff,
                   const uint32_t* sub, uint2* out, uint64_t out_cap, uint32_t* heavy, uint32_t* nheavy,
                   uint64_t* partials, uint64_t* res, hipStream_t s) {
   const uint32_t nblk = uint32_t((nslots + kBlock - 1) / kBlock);
   uint64_t* hoff = ctx->scratch[kScrD].as<uint64_t>();
   if (hipError_t e = ctx->ensure_ctl(); e != hipSuccess) return e;  // ctl words [64, 128): store sink
   auto launch = [&](auto slots_c, auto ck_c) {
-    constexpr bool SL = decltype(slots_c)::value, CK = decltype(ck_c)::value;
+    constexpr bool SL = decltype(slots_c)::value;
+    constexpr int CK = decltype(ck_c)::value;
     hipLaunchKernelGGL((k_expand_light<SL, CK>), dim3(nblk), dim3(kBlock), 0, s, src, nslots, ooff, sub, out, out_cap,
                        heavy, nheavy, partials, reinterpret_cast<uint2*>(ctx->ctl.as<uint64_t>() + 64));
     hipLaunchKernelGGL(k_heavy_offsets, dim3(1), dim3(1024), 0, s, heavy, nheavy, ooff, hoff);
@@ -713,17 +725,76 @@ hipError_t expand(hj3d_ctx* ctx, const SlotSrc& src, bool slots, bool ck, uint64
   };
   using T = std::true_type;
   using F = std::false_type;
+  using C0 = std::integral_constant<int, 0>;
+  using C1 = std::integral_constant<int, 1>;
   if (slots) {
-    if (ck) launch(T{}, T{});
-    else launch(T{}, F{});
+    if (ck == 2) launch(T{}, std::integral_constant<int, 2>{});
+    else if (ck) launch(T{}, C1{});
+    else launch(T{}, C0{});
   } else {
-    if (ck) launch(F{}, T{});
-    else launch(F{}, F{});
+    if (ck) launch(F{}, C1{});
+    else launch(F{}, C0{});
   }
   return hipGetLastError();
 }
 
+// hj3d_unnest's first pass: one slot per input pair {a, main_ref}, in the form the expansion takes
+// (output count, sub_off, a). A ref outside [0, n_mains) is skipped (0xFFFFFFFF = no match; a table
+// cleared or rebuilt smaller since the probe): count 0, and no main record is read for it.
+// 8 B read and 16 B written per pair.
+__global__ __launch_bounds__(kBlock) void k_unnest_slots(const uint2* __restrict__ in, uint64_t n,
+                                                         const uint4* __restrict__ mains, uint32_t n_mains,
+                                                         uint64_t* __restrict__ cnt, uint32_t* __restrict__ zo,
+                                                         uint32_t* __restrict__ po, uint64_t* __restrict__ res) {
+  uint64_t acc[kProbeFields] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += uint64_t(gridDim.x) * kBlock) {
+    const uint2 e = in[i];
+    const bool valid = e.y < n_mains;
+    uint4 M = make_uint4(0, 0, 0, 0);
+    if (valid) M = mains[e.y];
+    cnt[i] = M.w;
+    zo[i] = M.z;
+    po[i] = e.x;
+    acc[0] += 1;
+    acc[1] += valid;
+    acc[2] += M.w;
+  }
+  block_flush<kProbeFields, 1>(acc, res);
+}
+
 }  // namespace
+
+// AlgUnnestHt::step (algebra.hh:510-541) over n stored nested tuples {a, main_ref}: slots, scan, then
+// the materialised unnest's expansion (with out_cap = 0 it stores nothing and only folds the sums).
+hipError_t unnest_pairs(hj3d_ctx* ctx, const hj3d_table* t, const void* in, uint64_t n, uint32_t flags, void* out,
+                        uint64_t out_cap, uint64_t* res, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipError_t e;
+  const uint32_t nblk = uint32_t((n + kBlock - 1) / kBlock);
+  if ((e = ctx->scratch[kScrA].ensure((n + 1) * sizeof(uint64_t))) != hipSuccess) return e;
+  if ((e = ctx->scratch[kScrC].ensure(2 * n * sizeof(uint32_t) + 64)) != hipSuccess) return e;
+  if ((e = ctx->scratch[kScrSortK].ensure((n + 64) * sizeof(uint32_t))) != hipSuccess) return e;
+  if ((e = ctx->scratch[kScrD].ensure((n + 2) * sizeof(uint64_t))) != hipSuccess) return e;  // hoff
+  if ((e = ctx->scratch[kScrPartial].ensure(uint64_t(nblk) * kProbeFields * sizeof(uint64_t))) != hipSuccess) return e;
+  uint64_t* cnt = ctx->scratch[kScrA].as<uint64_t>();
+  uint32_t* zo = ctx->scratch[kScrC].as<uint32_t>() + 16;
+  uint32_t* po = zo + n;
+  uint32_t* nheavy = ctx->scratch[kScrSortK].as<uint32_t>();
+  uint32_t* heavy = nheavy + 64;
+  uint64_t* partials = ctx->scratch[kScrPartial].as<uint64_t>();
+  const uint4* mains = t->main.as<const uint4>();
+  const bool emit = (flags & HJ3D_PROBE_EMIT) && out;
+  if ((e = hipMemsetAsync(nheavy, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_unnest_slots, dim3(grid_for(ctx, n, kBlock * kItems)), dim3(kBlock), 0, s,
+                     static_cast<const uint2*>(in), n, mains, uint32_t(t->n_mains), cnt, zo, po, res);
+  if ((e = exclusive_scan_u64(ctx, cnt, cnt, n, s)) != hipSuccess) return e;
+  SlotSrc src{RelView{}, nullptr, mains, zo, po};
+  const int ck = (flags & HJ3D_PROBE_CHECKSUM) ? 1 : 2;  // the row sums always
+  if ((e = expand(ctx, src, true, ck, n, cnt, t->sub.as<const uint32_t>(), static_cast<uint2*>(out),
+                  emit ? out_cap : 0, heavy, nheavy, partials, res, s)) != hipSuccess)
+    return e;
+  return reduce_partials(partials, nblk, kProbeFields, 1, res, s);
+}
 
 hipError_t nested_build(hj3d_ctx* ctx, hj3d_table* t, const hj3d_rel& r, hipStream_t s) {
   hipError_t e;
@@ -795,7 +866,10 @@ hipError_t nested_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, u
   const unsigned g = grid_for(ctx, r.n, kBlock * kItems);
   hipError_t e;
   if (!unnest) {
-    if (emit)
+    if (emit && (flags & HJ3D_PROBE_MAINREF))
+      hipLaunchKernelGGL(k_nested_probe<kDenseRef>, dim3(g), dim3(kBlock), 0, s, v, t->fm, lo, nbl, off, mains, sub, o,
+                         out_cap, nullptr, nullptr, nullptr, nullptr, res);
+    else if (emit)
       hipLaunchKernelGGL(k_nested_probe<kDenseNU>, dim3(g), dim3(kBlock), 0, s, v, t->fm, lo, nbl, off, mains, sub, o,
                          out_cap, nullptr, nullptr, nullptr, nullptr, res);
     else
@@ -903,7 +977,8 @@ hipError_t radix_nested_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel
   uint32_t *zo = nullptr, *po = nullptr;
   Heavy* hq = nullptr;
   uint64_t* nhq = nullptr;
-  const int mode = !unnest ? (emit ? kDenseNU : kAggNU) : (emit ? kCountUN : kAggUN);
+  const int dense = (flags & HJ3D_PROBE_MAINREF) ? kDenseRef : kDenseNU;
+  const int mode = !unnest ? (emit ? dense : kAggNU) : (emit ? kCountUN : kAggUN);
   if (mode == kCountUN) {
     if ((e = ctx->scratch[kScrA].ensure((r.n + 1) * sizeof(uint64_t))) != hipSuccess) return e;
     if ((e = ctx->scratch[kScrC].ensure(3 * r.n * sizeof(uint32_t) + 64)) != hipSuccess) return e;
@@ -950,6 +1025,7 @@ hipError_t radix_nested_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel
     switch (mode) {
       case kAggNU: launch(std::integral_constant<int, kAggNU>{}); break;
       case kDenseNU: launch(std::integral_constant<int, kDenseNU>{}); break;
+      case kDenseRef: launch(std::integral_constant<int, kDenseRef>{}); break;
       case kAggUN: launch(std::integral_constant<int, kAggUN>{}); break;
       default: launch(std::integral_constant<int, kCountUN>{}); break;
     }

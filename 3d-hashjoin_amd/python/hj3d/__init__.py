@@ -24,6 +24,7 @@ HJ3D_OK, HJ3D_EINVAL, HJ3D_ENOMEM, HJ3D_EDEVICE, HJ3D_EUNSUPPORTED, HJ3D_EOVERFL
 HJ3D_ROW_IMPLICIT = 0xFFFFFFFF
 HJ3D_CHAIN, HJ3D_NESTED = 0, 1
 PROBE_UNIQUE, PROBE_UNNEST, PROBE_EMIT, PROBE_CHECKSUM, PROBE_ACCUMULATE = 0x1, 0x2, 0x4, 0x8, 0x10
+PROBE_MAINREF = 0x20
 T_BUILD, T_PROBE, T_PROBE_KERNEL, T_PARTITION, T_SCATTER, T_HIST = range(6)
 OPT_FORCE_DIRECT, OPT_RADIX_MIN, OPT_NESTED_SORT, OPT_SEL_UNFUSED, OPT_PACKED_PROBE = 1, 2, 4, 5, 6
 OPT_PROBE_ITEMS = 7
@@ -132,6 +133,8 @@ def lib():
         "hj3d_probe_result": (st, [p, C.POINTER(_ProbeRes)]),
         "hj3d_probe2": (st, [p, p, p, R, u32, p, u64]),
         "hj3d_probe2_result": (st, [p, C.POINTER(_Probe2Res)]),
+        "hj3d_unnest": (st, [p, p, p, u64, u32, p, u64]),
+        "hj3d_unnest2": (st, [p, p, p, p, u64, u32, p, u64]),
         "hj3d_partition": (st, [p, R, u64, u32, p, p]),
         "hj3d_partition_sel": (st, [p, R, C.POINTER(_SelPred), u32, u64, u32, p, p]),
         "hj3d_partition_strided": (st, [p, R, C.POINTER(_SelPred), u32, u64, u32, p, u64, p]),
@@ -358,12 +361,16 @@ class Context:
 
     # ---- probes ----
     def probe(self, table: "Table", rel: Rel, unique: bool = False, unnest: bool = False, out=None,
-              fetch: bool = True, checksum: bool = True, accumulate: bool = False) -> Optional[ProbeResult]:
+              fetch: bool = True, checksum: bool = True, accumulate: bool = False,
+              mainref: bool = False) -> Optional[ProbeResult]:
         """One probe strand. checksum=False skips the order-independent output checksums (a
         verification aid the reference does not compute); all counters stay exact.
-        accumulate=True adds to the previous probe's result (one strand issued in chunks)."""
+        accumulate=True adds to the previous probe's result (one strand issued in chunks).
+        mainref=True (nested table, out given, no unnest): the dense output pairs are {probe row,
+        main ref} (HJ3D_PROBE_MAINREF), the input of unnest / unnest2."""
         flags = (PROBE_UNIQUE if unique else 0) | (PROBE_UNNEST if unnest else 0) | \
-                (PROBE_CHECKSUM if checksum else 0) | (PROBE_ACCUMULATE if accumulate else 0)
+                (PROBE_CHECKSUM if checksum else 0) | (PROBE_ACCUMULATE if accumulate else 0) | \
+                (PROBE_MAINREF if mainref else 0)
         ptr, cap = None, 0
         if out is not None:
             flags |= PROBE_EMIT
@@ -407,6 +414,44 @@ class Context:
         d["overflow"] = st == HJ3D_EOVERFLOW
         return d
 
+    # ---- deferred unnesting (AlgUnnestHt as an operator of its own) ----
+    @staticmethod
+    def _words(t, words: int, what: str):
+        torch = _torch()
+        if not t.is_cuda or t.dtype not in (torch.int32, torch.uint32) or t.dim() != 2 or t.shape[1] != words or \
+                not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous (n, {words}) int32 device tensor")
+        return (t.data_ptr() if t.shape[0] else None), t.shape[0]
+
+    def unnest(self, table: "Table", nested, out=None, checksum: bool = True, fetch: bool = True) -> Optional[ProbeResult]:
+        """hj3d_unnest: the stored nested tuples `nested` ((n, 2) int32 device tensor of {a, main ref}
+        as probe(mainref=True) wrote them, filtered / reordered / concatenated at will; invalid refs
+        are skipped) expanded to {a, build row} pairs. out: a contiguous (cap, 2) int32 device tensor
+        (None: counters and sums only). n_out counts all pairs; `overflow` tells whether some did not
+        fit. checksum=False leaves out the pair hashes (sum_h, xor_h)."""
+        ptr_in, n = self._words(nested, 2, "nested")
+        flags = PROBE_CHECKSUM if checksum else 0
+        ptr, cap = None, 0
+        if out is not None:
+            ptr, cap = self._words(out, 2, "out")
+            flags |= PROBE_EMIT
+        self._check(lib().hj3d_unnest(self.h, table.h, ptr_in, n, flags, ptr, cap), "hj3d_unnest")
+        return self.probe_result() if fetch else None
+
+    def unnest2(self, ts: "Table", tt: "Table", nested, out=None, checksum: bool = True,
+                fetch: bool = True) -> Optional[dict]:
+        """hj3d_unnest2: triples {a, ref_s, ref_t} ((n, 3) int32 device tensor; main refs of ts and tt)
+        expanded to every {a, s_row, t_row} of the two groups. out: a contiguous (cap, 3) int32 device
+        tensor or None; the result is probe2's dict (c_unnest_1, c_unnest_2, c_top, sums, overflow)."""
+        ptr_in, n = self._words(nested, 3, "nested")
+        flags = PROBE_CHECKSUM if checksum else 0
+        ptr, cap = None, 0
+        if out is not None:
+            ptr, cap = self._words(out, 3, "out")
+            flags |= PROBE_EMIT
+        self._check(lib().hj3d_unnest2(self.h, ts.h, tt.h, ptr_in, n, flags, ptr, cap), "hj3d_unnest2")
+        return self.probe2_result() if fetch else None
+
     # ---- selection pushdown (AlgSelection / AlgDynSelection, algebra.hh:278-358) ----
     def select(self, rel: Rel, preds, out_pairs=None, count=None, fetch: bool = True):
         """Tuples of `rel` whose conjunction of predicates holds, as a stable (key, row) pair
@@ -433,12 +478,13 @@ class Context:
         return out_pairs, Rel(out_pairs, 0, 1, n=n), n
 
     def probe_sel(self, table: "Table", rel: Rel, preds, unique: bool = False, unnest: bool = False, out=None,
-                  fetch: bool = True, checksum: bool = True) -> Optional[ProbeResult]:
+                  fetch: bool = True, checksum: bool = True, mainref: bool = False) -> Optional[ProbeResult]:
         """scan(rel) -> selection(preds) -> probe (hj3d_probe_sel): the selection fused into the
         probe partitioner where it applies. n_probe of the result = the passing tuples."""
         if len(preds) > SEL_MAX:
             raise ValueError(f"at most {SEL_MAX} predicates")
-        flags = (PROBE_UNIQUE if unique else 0) | (PROBE_UNNEST if unnest else 0) | (PROBE_CHECKSUM if checksum else 0)
+        flags = (PROBE_UNIQUE if unique else 0) | (PROBE_UNNEST if unnest else 0) | \
+                (PROBE_CHECKSUM if checksum else 0) | (PROBE_MAINREF if mainref else 0)
         ptr, cap = None, 0
         if out is not None:
             flags |= PROBE_EMIT

@@ -15,6 +15,9 @@
  *                              and with HJ3D_PROBE_UNNEST also AlgUnnestHt::step  algebra.hh:510-541
  *   hj3d_probe2                the experiment-4 probe strand: two probes keyed on the same
  *                              probe attribute + deferred unnesting   main_experiment4.cc:831-1043
+ *   hj3d_unnest                AlgUnnestHt::step as a separate operator over stored nested tuples
+ *                              {a, main ref} (HJ3D_PROBE_MAINREF)     algebra.hh:490-541
+ *   hj3d_unnest2               the two stacked unnests of experiment 4  main_experiment4.cc:435-466
  *   hj3d_table_stats           HtChaining1/HtNested1::makeStatistics  ht_chaining.hh:260-292,
  *                                                                     ht_nested.hh:450-482
  *   hj3d_table_clear           HtChaining1/HtNested1::clear           ht_chaining.hh:250-258,
@@ -99,6 +102,15 @@ typedef struct {
                                        restarting it (one probe strand issued in chunks) */
 #define HJ3D_PROBE_CHECKSUM 0x8u /* fold sum_a/sum_b/sum_h/xor_h over the output (verification;
                                     the reference itself only counts); counts are always exact */
+/* HJ3D_PROBE_MAINREF: the nested result tuple carries its group, as AlgNestJoinProbe's output
+ * {probe tuple, MainNode*} does (algebra.hh:435-459). Nested table only, with HJ3D_PROBE_EMIT and
+ * without HJ3D_PROBE_UNNEST (anything else: HJ3D_EINVAL). The dense output slot of a probe tuple is
+ * then {u32 probe row, u32 main_ref}: main_ref = the index of the matched main record in the table's
+ * main-record array (the index into hj3d_table_export's `payload`), 0xFFFFFFFF without a match.
+ * Counters and checksums are those of the probe without the flag (sum_b / sum_h / xor_h fold the first
+ * build row). hj3d_unnest / hj3d_unnest2 expand such refs later. A ref is valid until the table's next
+ * hj3d_build, hj3d_build_many or hj3d_table_clear. */
+#define HJ3D_PROBE_MAINREF 0x20u
 
 /* Result of one probe strand. Orientation follows the reference's concat functors:
  * a = probe-side row, b = build-side row (for a nested probe without unnest, b = the row of
@@ -346,6 +358,38 @@ hj3d_status hj3d_probe_result(hj3d_ctx* ctx, hj3d_probe_res* out);
 hj3d_status hj3d_probe2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const hj3d_rel* probe,
                         uint32_t flags, void* out_dev, uint64_t out_cap);
 hj3d_status hj3d_probe2_result(hj3d_ctx* ctx, hj3d_probe2_res* out);
+
+/* ---- deferred unnesting as operators of their own ----
+ * hj3d_unnest replaces AlgUnnestHt::step (algebra.hh:490-541) stacked anywhere downstream of a nested
+ * probe (main_algebra_example.cc:305-316). nested_dev: n stored nested tuples {u32 a, u32 main_ref}
+ * (8 bytes each) in device memory: what a HJ3D_PROBE_MAINREF probe of `t` wrote, possibly filtered,
+ * reordered or concatenated since. A tuple whose ref is 0xFFFFFFFF (no match), or not below the
+ * table's current main-record count (the table was cleared or rebuilt smaller since the probe), is
+ * skipped; no memory is read through such a ref. Every other tuple yields {a, row} for each build row
+ * of main record main_ref (sub[sub_off .. sub_off + sub_len)): with HJ3D_PROBE_EMIT, pairs
+ * {u32 a, u32 build row} to out_dev, at most out_cap of them, in no specified order; nothing is
+ * written at or beyond out_dev + 8 * out_cap. Without EMIT only the counters and sums are computed.
+ * flags: HJ3D_PROBE_EMIT and HJ3D_PROBE_CHECKSUM only. HJ3D_EINVAL: any other flag, a chaining
+ * table, EMIT with out_dev == NULL and out_cap > 0, n >= 2^32. Asynchronous; a nested build still
+ * pending is finished first, as by a probe. The result goes to the probe result slot
+ * (hj3d_probe_result): n_probe = n, n_matched = tuples with a valid ref, n_out = output pairs
+ * (c_unnest), n_cmps = 0, sum_a / sum_b always, sum_h / xor_h only with HJ3D_PROBE_CHECKSUM (else 0);
+ * HJ3D_EOVERFLOW (with the complete counters) if n_out > out_cap. */
+hj3d_status hj3d_unnest(hj3d_ctx* ctx, const hj3d_table* t, const void* nested_dev, uint64_t n, uint32_t flags,
+                        void* out_dev, uint64_t out_cap);
+/* hj3d_unnest2 replaces the two stacked unnest functors of experiment 4 (main_experiment4.cc:435-466)
+ * without hj3d_probe2's restriction to one probe attribute: nested_dev holds n triples
+ * {u32 a, u32 ref_s, u32 ref_t} (12 bytes each, 4-byte aligned), ref_s a main ref of ts and ref_t one
+ * of tt (both HJ3D_NESTED; their geometries may differ). A triple with an invalid ref (the rule of
+ * hj3d_unnest, per table) is skipped; every other yields {a, s_row, t_row} for each combination of the
+ * two groups' rows. Output layout, capacity rule and order as hj3d_probe2 with HJ3D_PROBE_EMIT.
+ * flags: HJ3D_PROBE_EMIT and HJ3D_PROBE_CHECKSUM only; HJ3D_EINVAL as for hj3d_unnest. The result
+ * goes to the hj3d_probe2 result slot (hj3d_probe2_result): c_unnest_1 = sum of |T group| (the
+ * reference unnests T first), c_unnest_2 = c_top = sum of |S group| * |T group|, c_probe_* = 0,
+ * sum_a / sum_b / sum_c always, sum_h / xor_h only with HJ3D_PROBE_CHECKSUM; HJ3D_EOVERFLOW (complete
+ * counters) if c_top > out_cap. */
+hj3d_status hj3d_unnest2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const void* nested_dev,
+                         uint64_t n, uint32_t flags, void* out_dev, uint64_t out_cap);
 
 /* ---- multi-GPU exchange helpers (bucket-range radix partition) ----
  * Destination of a tuple: owner(bucket) = bucket * nparts / num_buckets. Writes (key,row)
