@@ -55,10 +55,22 @@ bool rel_ok(const hj3d_rel* r) {
   return true;
 }
 
+hj3d_status fail_in(hj3d_ctx* ctx, const char* entry, const char* what) {
+  char buf[256];
+  std::snprintf(buf, sizeof(buf), "%s: %s", entry, what);
+  return fail(ctx, HJ3D_EINVAL, buf);
+}
+
+// the hj3d_gen_* entries' tuple array
+bool tuples_ok(uint64_t n, const void* tuples, uint32_t stride, uint32_t key_off) {
+  return (!n || tuples) && stride != 0 && !(stride & 3) && !(key_off & 3) && key_off + 4 <= stride;
+}
+
 // (kResFields: hj3d_device.hpp)
-// result-slot words beyond the counters: n_out before the current probe call, and a sticky flag
-// set when a call's non-dense output exceeded its own buffer (accumulated strands included)
-constexpr int kResOutMark = 14, kResOvf = 15;
+// result-slot words the host plumbing reads by name: the n_out counter, and beyond the counters n_out
+// before the current probe call and a sticky flag set when a call's non-dense output exceeded its own
+// buffer (accumulated strands included)
+constexpr int kResNOut = 2, kResOutMark = 14, kResOvf = 15;
 
 __global__ void k_out_overflow(uint64_t* res, uint64_t cap) {
   if (threadIdx.x == 0 && res[2] - res[kResOutMark] > cap) res[kResOvf] = 1;
@@ -70,18 +82,38 @@ bool dense_output(const hj3d_table* t, uint32_t flags) {
 
 // Non-dense EMIT probes (chains without early exit, unnest) write as many pairs as they find; the
 // kernels drop pairs past out_cap. Mark n_out before the call and compare after it, on the stream.
-hipError_t out_mark(hj3d_ctx* ctx, const hj3d_table* t, uint32_t flags) {
-  if (!(flags & HJ3D_PROBE_EMIT) || dense_output(t, flags)) return hipSuccess;
-  // a fresh strand's result slot was just zeroed: its mark (word 14) equals n_out (word 2) = 0
+hipError_t out_mark(hj3d_ctx* ctx, bool dense, uint32_t flags) {
+  if (!(flags & HJ3D_PROBE_EMIT) || dense) return hipSuccess;
+  // a fresh strand's result slot was just zeroed: its mark equals n_out = 0
   if (!(flags & HJ3D_PROBE_ACCUMULATE)) return hipSuccess;
   uint64_t* res = ctx->res.as<uint64_t>();
-  return hipMemcpyAsync(res + kResOutMark, res + 2, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream);
+  return hipMemcpyAsync(res + kResOutMark, res + kResNOut, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream);
 }
 
-hipError_t out_check(hj3d_ctx* ctx, const hj3d_table* t, uint32_t flags, uint64_t out_cap) {
-  if (!(flags & HJ3D_PROBE_EMIT) || dense_output(t, flags)) return hipSuccess;
+hipError_t out_check(hj3d_ctx* ctx, bool dense, uint32_t flags, uint64_t out_cap) {
+  if (!(flags & HJ3D_PROBE_EMIT) || dense) return hipSuccess;
+  static_assert(kResNOut == 2, "k_out_overflow compares res[2]");
   hipLaunchKernelGGL(k_out_overflow, dim3(1), dim3(64), 0, ctx->stream, ctx->res.as<uint64_t>(), out_cap);
   return hipGetLastError();
+}
+
+// remember what an overflow check needs (hj3d_probe_result); n = the call's probe tuples
+void note_probe(hj3d_ctx* ctx, bool dense, uint32_t flags, uint64_t n, uint64_t out_cap) {
+  const bool acc = flags & HJ3D_PROBE_ACCUMULATE;
+  ctx->res_flags = flags;
+  ctx->res_dense = dense;
+  ctx->res_cap = (flags & HJ3D_PROBE_EMIT) ? out_cap : ~0ull;
+  ctx->res_nprobe = acc ? ctx->res_nprobe + n : n;
+  // dense output: each call needs one slot per probe tuple of its own buffer
+  const bool ovf_dense = dense && (flags & HJ3D_PROBE_EMIT) && n > out_cap;
+  ctx->res_overflow = (acc && ctx->res_overflow) || ovf_dense;
+  ctx->res_accumulated = acc;
+}
+
+// the same for hj3d_probe2_result (c_top against the capacity)
+void note_probe2(hj3d_ctx* ctx, uint32_t flags, uint64_t out_cap) {
+  ctx->res2_flags = flags;
+  ctx->res2_cap = (flags & HJ3D_PROBE_EMIT) ? out_cap : ~0ull;
 }
 
 // The fused build partition's grid barrier (radix.hip k_rp_fused) sets word 1 of ctx->gbar when a
@@ -111,7 +143,175 @@ hj3d_status table_gbar_check(hj3d_ctx* ctx, const hj3d_table* t) {
   return fail(ctx, HJ3D_EDEVICE, "fused build partition: a grid barrier timed out, the table is invalid (rebuild it)");
 }
 
+// The result slot on the host, for both result getters: copied behind the strand, with the barrier word.
+hj3d_status read_result(hj3d_ctx* ctx, const char* what, uint64_t h[kResFields]) {
+  uint64_t gw = 0;
+  hipError_t e = hipMemcpyAsync(h, ctx->res.p, kResFields * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = gbar_copy(ctx, &gw);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) return from_hip(ctx, e, what);
+  return gbar_check(ctx, gw);
+}
+
+// The partitioned probe sizes its LDS slices by the number of main records: a nested build's counts
+// (word 1 = main records; word 3 = the aggregation build's give-up flag) travel to pinned host
+// memory behind the build and are read at the table's next use (table_resolve), so consecutive
+// builds (experiment 4's two tables) do not wait for each other.
+// The aggregation builds write the host copy from their last kernel (k_nagg_mains), so their pinned
+// mirror must exist before the build (nested_host_counts); the other nested builds copy it.
+hipError_t nested_host_counts(hj3d_table* t) {
+  hipError_t e = hipSuccess;
+  if (!t->hc) {
+    e = hipHostMalloc(reinterpret_cast<void**>(&t->hc), 4 * sizeof(uint64_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->hc_ev, hipEventDisableTiming);
+  }
+  return e;
+}
+hipError_t nested_pending(hj3d_ctx* ctx, hj3d_table* t, const hj3d_rel& build, bool agg) {
+  hipError_t e = nested_host_counts(t);
+  // (agg: k_nagg_mains wrote the mirror)
+  if (e == hipSuccess && !agg)
+    e = hipMemcpyAsync(t->hc, t->counts.p, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipEventRecord(t->hc_ev, ctx->stream);
+  t->pending = e == hipSuccess;
+  t->pending_agg = agg;
+  t->pending_rel = build;
+  t->pending_ctx = ctx;
+  t->n_mains = 0;
+  return e;
+}
+
+// A build replaces the table's content: a build in flight for the old content is dropped (its copy
+// stays stream-ordered), and so is the fused build partition's barrier tag (set again by that
+// partition; no nested build records one).
+void begin_build(hj3d_table* t) {
+  t->pending = false;
+  t->gbar_tag = 0;
+}
+
+// A build whose partition / slice / region scratch did not fit hands over to the next, leaner build,
+// as one that does not apply does.
+hipError_t oom_is_unsupported(hipError_t e) {
+  if (e != hipErrorOutOfMemory) return e;
+  (void)hipGetLastError();
+  return hipErrorNotSupported;
+}
+
+hipError_t build_one(hj3d_ctx* ctx, hj3d_table* t, const hj3d_rel* build) {
+  PhaseTimer tm(ctx, HJ3D_T_BUILD);
+  hipError_t e;
+  begin_build(t);
+  if (t->desc.kind == HJ3D_CHAIN) {
+    bool sorted = false;
+    t->path = "radix";
+    e = (!ctx->force_direct && !ctx->pk_build && build->n >= (ctx->radix_min >> 4) && build->n > 0 &&
+         t->nb_local >= 64)
+            ? radix_build(ctx, t, *build, ctx->stream, &sorted)
+            : hipErrorNotSupported;
+    if (e == hipErrorNotSupported && build->n >= (ctx->radix_min >> 4)) {
+      t->path = "slices";
+      // tables beyond the radix build's 2048 x 16384 buckets (the direct build needs far less scratch)
+      e = oom_is_unsupported(pk_build(ctx, t, *build, ctx->stream));
+      sorted = e == hipSuccess;
+    }
+    if (e == hipErrorNotSupported) {
+      t->path = "direct";
+      e = chain_build(ctx, t, *build, ctx->stream);
+    }
+    if (e == hipSuccess && !sorted) e = sort_small_buckets(ctx, t, ctx->stream);
+  } else {
+    e = hipErrorNotSupported;
+    bool agg = false;
+    if (!ctx->nested_sort) {
+      e = nested_host_counts(t);
+      if (e == hipSuccess) e = nested_build_agg(ctx, t, *build, ctx->stream, &t->path);
+      e = oom_is_unsupported(e);  // then the sort build
+      agg = e == hipSuccess;
+    }
+    if (e == hipErrorNotSupported) {
+      t->path = "nested_sort";
+      e = nested_build(ctx, t, *build, ctx->stream);
+    }
+    if (e == hipSuccess) e = nested_pending(ctx, t, *build, agg);
+  }
+  t->built = e == hipSuccess;
+  return e;
+}
+
+hipError_t resolve(hj3d_ctx* ctx, const hj3d_table* t) { return table_resolve(ctx, const_cast<hj3d_table*>(t)); }
+
+// HJ3D_PROBE_MAINREF: the dense slot of a nested probe tuple carries the matched main record's index
+bool mainref_ok(const hj3d_table* t, uint32_t flags) {
+  return !(flags & HJ3D_PROBE_MAINREF) ||
+         (t->desc.kind == HJ3D_NESTED && (flags & HJ3D_PROBE_EMIT) && !(flags & HJ3D_PROBE_UNNEST));
+}
+
+bool sel_ok(const hj3d_rel* rel, const hj3d_sel_pred* preds, uint32_t npred) {
+  if (npred > HJ3D_SEL_MAX || (npred && !preds)) return false;
+  for (uint32_t k = 0; k < npred; ++k)
+    if ((preds[k].word_off & 3) || preds[k].word_off + 4 > rel->stride || preds[k].op > HJ3D_SEL_RANGE) return false;
+  return true;
+}
+
+// Argument checks the probe-like entries share, each HJ3D_OK or HJ3D_EINVAL with the entry's name in
+// the message.
+hj3d_status unnest_flags_ok(hj3d_ctx* ctx, const char* entry, uint32_t flags) {
+  return (flags & ~(HJ3D_PROBE_EMIT | HJ3D_PROBE_CHECKSUM)) ? fail_in(ctx, entry, "flags other than EMIT, CHECKSUM")
+                                                            : HJ3D_OK;
+}
+hj3d_status emit_buffer_ok(hj3d_ctx* ctx, const char* entry, uint32_t flags, const void* out_dev, uint64_t out_cap) {
+  return (flags & HJ3D_PROBE_EMIT) && !out_dev && out_cap ? fail_in(ctx, entry, "EMIT without buffer") : HJ3D_OK;
+}
+hj3d_status probe_args_ok(hj3d_ctx* ctx, const char* entry, const hj3d_table* t, const hj3d_rel* probe, uint32_t flags,
+                          const void* out_dev, uint64_t out_cap) {
+  if (!ctx || !t) return HJ3D_EINVAL;
+  if (!rel_ok(probe)) return fail_in(ctx, entry, "invalid relation");
+  if (const hj3d_status st = emit_buffer_ok(ctx, entry, flags, out_dev, out_cap); st != HJ3D_OK) return st;
+  if ((flags & HJ3D_PROBE_UNNEST) && t->desc.kind != HJ3D_NESTED) return fail_in(ctx, entry, "UNNEST needs a nested table");
+  if (!mainref_ok(t, flags)) return fail_in(ctx, entry, "MAINREF needs a nested table, EMIT and no UNNEST");
+  return HJ3D_OK;
+}
+
 }  // namespace
+
+namespace hj3d {
+hipError_t table_resolve(hj3d_ctx* ctx, hj3d_table* t) {
+  if (!t->pending) return hipSuccess;
+  t->pending = false;
+  // polled, not waited for: the build is short (config E: ~0.3 ms) and the probe's launches follow
+  // as soon as it lands (a blocking wait's wake-up left the GPU idle for ~20 us)
+  // A short build lands within the spin; past 50 us the loop yields its core to other host threads
+  // (an RCCL proxy, other ranks), and past 20 ms it blocks.
+  hipError_t e;
+  const auto t0 = std::chrono::steady_clock::now();
+  while ((e = hipEventQuery(t->hc_ev)) == hipErrorNotReady) {
+    const auto us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    if (us > 20000) {
+      e = hipEventSynchronize(t->hc_ev);
+      break;
+    }
+    if (us > 50) sched_yield();
+  }
+  if (e != hipSuccess) {
+    t->built = false;
+    return e;
+  }
+  uint64_t hc[4];
+  std::memcpy(hc, t->hc, sizeof(hc));
+  if (t->pending_agg && uint32_t(hc[3]) != 0) {  // a key range too dense for the LDS table
+    // the rest of the build: timed as build work (not inside the probe that triggered it)
+    PhaseTimer tm(ctx, HJ3D_T_BUILD);
+    t->path = "nested_sort";
+    t->gbar_tag = 0;  // the content is replaced: counts word 3 becomes the sort build's largest key
+    e = nested_build(ctx, t, t->pending_rel, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hc, t->counts.p, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  }
+  t->n_mains = e == hipSuccess ? hc[1] : 0;
+  t->built = e == hipSuccess;
+  return e;
+}
+}  // namespace hj3d
 
 extern "C" {
 
@@ -372,34 +572,6 @@ hj3d_status hj3d_table_clear(hj3d_ctx* ctx, hj3d_table* t) {
   return from_hip(ctx, e, "hj3d_table_clear");
 }
 
-// The partitioned probe sizes its LDS slices by the number of main records: a nested build's counts
-// (word 1 = main records; word 3 = the aggregation build's give-up flag) travel to pinned host
-// memory behind the build and are read at the table's next use (table_resolve), so consecutive
-// builds (experiment 4's two tables) do not wait for each other.
-// The aggregation builds write the host copy from their last kernel (k_nagg_mains), so their pinned
-// mirror must exist before the build (nested_host_counts); the other nested builds copy it.
-static hipError_t nested_host_counts(hj3d_table* t) {
-  hipError_t e = hipSuccess;
-  if (!t->hc) {
-    e = hipHostMalloc(reinterpret_cast<void**>(&t->hc), 4 * sizeof(uint64_t), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->hc_ev, hipEventDisableTiming);
-  }
-  return e;
-}
-static hipError_t nested_pending(hj3d_ctx* ctx, hj3d_table* t, const hj3d_rel& build, bool agg) {
-  hipError_t e = nested_host_counts(t);
-  // (agg: k_nagg_mains wrote the mirror)
-  if (e == hipSuccess && !agg)
-    e = hipMemcpyAsync(t->hc, t->counts.p, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipEventRecord(t->hc_ev, ctx->stream);
-  t->pending = e == hipSuccess;
-  t->pending_agg = agg;
-  t->pending_rel = build;
-  t->pending_ctx = ctx;
-  t->n_mains = 0;
-  return e;
-}
-
 hj3d_status hj3d_build_many(hj3d_ctx* ctx, hj3d_table* const* tables, const hj3d_rel* builds, uint32_t count) {
   if (!ctx || (count && (!tables || !builds))) return HJ3D_EINVAL;
   for (uint32_t k = 0; k < count; ++k) {
@@ -415,18 +587,12 @@ hj3d_status hj3d_build_many(hj3d_ctx* ctx, hj3d_table* const* tables, const hj3d
     const char* path = "nested_agg";
     {
       PhaseTimer tm(ctx, HJ3D_T_BUILD);
-      for (uint32_t k = 0; k < 2; ++k) {
-        tables[k]->pending = false;
-        tables[k]->gbar_tag = 0;  // (as build_one: no nested build records a barrier tag)
-      }
+      for (uint32_t k = 0; k < 2; ++k) begin_build(tables[k]);
       e = nested_host_counts(tables[0]);
       if (e == hipSuccess) e = nested_host_counts(tables[1]);
       if (e == hipSuccess) e = nested_build_agg_many(ctx, tables, builds, 2, ctx->stream, &path);
     }
-    if (e == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      e = hipErrorNotSupported;
-    }
+    e = oom_is_unsupported(e);
     if (e != hipErrorNotSupported) {
       for (uint32_t k = 0; k < 2 && e == hipSuccess; ++k) {
         tables[k]->path = path;
@@ -444,58 +610,6 @@ hj3d_status hj3d_build_many(hj3d_ctx* ctx, hj3d_table* const* tables, const hj3d
   return HJ3D_OK;
 }
 
-}  // extern "C"
-
-static hipError_t build_one(hj3d_ctx* ctx, hj3d_table* t, const hj3d_rel* build) {
-  PhaseTimer tm(ctx, HJ3D_T_BUILD);
-  hipError_t e;
-  t->pending = false;  // a build in flight for the old content is replaced (its copy stays stream-ordered)
-  t->gbar_tag = 0;     // (set again by a fused build partition)
-  if (t->desc.kind == HJ3D_CHAIN) {
-    bool sorted = false;
-    t->path = "radix";
-    e = (!ctx->force_direct && !ctx->pk_build && build->n >= (ctx->radix_min >> 4) && build->n > 0 &&
-         t->nb_local >= 64)
-            ? radix_build(ctx, t, *build, ctx->stream, &sorted)
-            : hipErrorNotSupported;
-    if (e == hipErrorNotSupported && build->n >= (ctx->radix_min >> 4)) {
-      t->path = "slices";
-      e = pk_build(ctx, t, *build, ctx->stream);  // tables beyond the radix build's 2048 x 16384 buckets
-      if (e == hipErrorOutOfMemory) {  // its region scratch did not fit: the direct build needs far less
-        (void)hipGetLastError();
-        e = hipErrorNotSupported;
-      }
-      sorted = e == hipSuccess;
-    }
-    if (e == hipErrorNotSupported) {
-      t->path = "direct";
-      e = chain_build(ctx, t, *build, ctx->stream);
-    }
-    if (e == hipSuccess && !sorted) e = sort_small_buckets(ctx, t, ctx->stream);
-  } else {
-    e = hipErrorNotSupported;
-    bool agg = false;
-    if (!ctx->nested_sort) {
-      e = nested_host_counts(t);
-      if (e == hipSuccess) e = nested_build_agg(ctx, t, *build, ctx->stream, &t->path);
-      if (e == hipErrorOutOfMemory) {  // partition / slice scratch did not fit: the sort build
-        (void)hipGetLastError();
-        e = hipErrorNotSupported;
-      }
-      agg = e == hipSuccess;
-    }
-    if (e == hipErrorNotSupported) {
-      t->path = "nested_sort";
-      e = nested_build(ctx, t, *build, ctx->stream);
-    }
-    if (e == hipSuccess) e = nested_pending(ctx, t, *build, agg);
-  }
-  t->built = e == hipSuccess;
-  return e;
-}
-
-extern "C" {
-
 hj3d_status hj3d_build(hj3d_ctx* ctx, hj3d_table* t, const hj3d_rel* build) {
   if (!ctx || !t) return HJ3D_EINVAL;
   if (!rel_ok(build)) return fail(ctx, HJ3D_EINVAL, "hj3d_build: invalid relation");
@@ -505,53 +619,6 @@ hj3d_status hj3d_build(hj3d_ctx* ctx, hj3d_table* t, const hj3d_rel* build) {
   if (e == hipSuccess && ctx->sync_build) e = table_resolve(ctx, t);
   return from_hip(ctx, e, "hj3d_build");
 }
-
-}  // extern "C"
-
-namespace hj3d {
-hipError_t table_resolve(hj3d_ctx* ctx, hj3d_table* t) {
-  if (!t->pending) return hipSuccess;
-  t->pending = false;
-  // polled, not waited for: the build is short (config E: ~0.3 ms) and the probe's launches follow
-  // as soon as it lands (a blocking wait's wake-up left the GPU idle for ~20 us)
-  // A short build lands within the spin; past 50 us the loop yields its core to other host threads
-  // (an RCCL proxy, other ranks), and past 20 ms it blocks.
-  hipError_t e;
-  const auto t0 = std::chrono::steady_clock::now();
-  while ((e = hipEventQuery(t->hc_ev)) == hipErrorNotReady) {
-    const auto us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-    if (us > 20000) {
-      e = hipEventSynchronize(t->hc_ev);
-      break;
-    }
-    if (us > 50) sched_yield();
-  }
-  if (e != hipSuccess) {
-    t->built = false;
-    return e;
-  }
-  uint64_t hc[4];
-  std::memcpy(hc, t->hc, sizeof(hc));
-  if (t->pending_agg && uint32_t(hc[3]) != 0) {  // a key range too dense for the LDS table
-    // the rest of the build: timed as build work (not inside the probe that triggered it)
-    PhaseTimer tm(ctx, HJ3D_T_BUILD);
-    t->path = "nested_sort";
-    t->gbar_tag = 0;  // the content is replaced: counts word 3 becomes the sort build's largest key
-    e = nested_build(ctx, t, t->pending_rel, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hc, t->counts.p, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  }
-  t->n_mains = e == hipSuccess ? hc[1] : 0;
-  t->built = e == hipSuccess;
-  return e;
-}
-}  // namespace hj3d
-
-static hipError_t resolve(hj3d_ctx* ctx, const hj3d_table* t) {
-  return table_resolve(ctx, const_cast<hj3d_table*>(t));
-}
-
-extern "C" {
 
 const char* hj3d_table_build_path(const hj3d_table* t) {
   if (!t || !t->built) return "none";
@@ -614,48 +681,18 @@ hj3d_status hj3d_table_size(hj3d_ctx* ctx, const hj3d_table* t, uint64_t* n_entr
   return HJ3D_OK;
 }
 
-// remember what an overflow check needs (hj3d_probe_result)
-static void note_probe(hj3d_ctx* ctx, const hj3d_table* t, uint64_t n, uint32_t flags, uint64_t out_cap) {
-  const bool acc = flags & HJ3D_PROBE_ACCUMULATE;
-  ctx->res_flags = flags;
-  ctx->res_dense = dense_output(t, flags);
-  ctx->res_cap = (flags & HJ3D_PROBE_EMIT) ? out_cap : ~0ull;
-  ctx->res_nprobe = acc ? ctx->res_nprobe + n : n;
-  // dense output: each call needs one slot per probe tuple of its own buffer
-  const bool ovf_dense = ctx->res_dense && (flags & HJ3D_PROBE_EMIT) && n > out_cap;
-  ctx->res_overflow = (acc && ctx->res_overflow) || ovf_dense;
-  ctx->res_accumulated = acc;
-}
-
-// HJ3D_PROBE_MAINREF: the dense slot of a nested probe tuple carries the matched main record's index
-static bool mainref_ok(const hj3d_table* t, uint32_t flags) {
-  return !(flags & HJ3D_PROBE_MAINREF) ||
-         (t->desc.kind == HJ3D_NESTED && (flags & HJ3D_PROBE_EMIT) && !(flags & HJ3D_PROBE_UNNEST));
-}
-
-static bool sel_ok(const hj3d_rel* rel, const hj3d_sel_pred* preds, uint32_t npred) {
-  if (npred > HJ3D_SEL_MAX || (npred && !preds)) return false;
-  for (uint32_t k = 0; k < npred; ++k)
-    if ((preds[k].word_off & 3) || preds[k].word_off + 4 > rel->stride || preds[k].op > HJ3D_SEL_RANGE) return false;
-  return true;
-}
-
 hj3d_status hj3d_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* probe, uint32_t flags, void* out_dev,
                        uint64_t out_cap) {
-  if (!ctx || !t) return HJ3D_EINVAL;
-  if (!rel_ok(probe)) return fail(ctx, HJ3D_EINVAL, "hj3d_probe: invalid relation");
-  if ((flags & HJ3D_PROBE_EMIT) && !out_dev && out_cap) return fail(ctx, HJ3D_EINVAL, "hj3d_probe: EMIT without buffer");
-  if ((flags & HJ3D_PROBE_UNNEST) && t->desc.kind != HJ3D_NESTED)
-    return fail(ctx, HJ3D_EINVAL, "hj3d_probe: UNNEST needs a nested table");
-  if (!mainref_ok(t, flags)) return fail(ctx, HJ3D_EINVAL, "hj3d_probe: MAINREF needs a nested table, EMIT and no UNNEST");
+  if (const hj3d_status st = probe_args_ok(ctx, "hj3d_probe", t, probe, flags, out_dev, out_cap); st != HJ3D_OK) return st;
   if (hipError_t re = resolve(ctx, t); re != hipSuccess) return from_hip(ctx, re, "hj3d_probe");
   PhaseTimer tm(ctx, HJ3D_T_PROBE);
   uint64_t* res = ctx->res.as<uint64_t>();
   const bool acc = flags & HJ3D_PROBE_ACCUMULATE;
+  const bool dense = dense_output(t, flags);
   if (pk_probe_applicable(ctx, t, probe->n, flags)) {  // the packed unique probe sets res itself
     hipError_t e = pk_probe(ctx, t, *probe, flags, out_dev, out_cap, res, ctx->stream);
     if (e != hipErrorNotSupported) {
-      note_probe(ctx, t, probe->n, flags, out_cap);
+      note_probe(ctx, dense, flags, probe->n, out_cap);
       return from_hip(ctx, e, "hj3d_probe");
     }
   }
@@ -665,7 +702,7 @@ hj3d_status hj3d_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* probe
   ZeroList zres;
   zres.add(res, kResFields);
   hipError_t e = acc || nested_radix ? hipSuccess : hipMemsetAsync(res, 0, kResFields * sizeof(uint64_t), ctx->stream);
-  if (e == hipSuccess) e = out_mark(ctx, t, flags);
+  if (e == hipSuccess) e = out_mark(ctx, dense, flags);
   if (e == hipSuccess) {
     e = hipErrorNotSupported;
     if (t->desc.kind == HJ3D_CHAIN && radix_probe_applicable(ctx, t, probe->n))
@@ -682,23 +719,19 @@ hj3d_status hj3d_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* probe
                                        : nested_probe(ctx, t, *probe, flags, out_dev, out_cap, res, ctx->stream);
     }
   }
-  if (e == hipSuccess) e = out_check(ctx, t, flags, out_cap);
-  note_probe(ctx, t, probe->n, flags, out_cap);
+  if (e == hipSuccess) e = out_check(ctx, dense, flags, out_cap);
+  note_probe(ctx, dense, flags, probe->n, out_cap);
   return from_hip(ctx, e, "hj3d_probe");
 }
 
 hj3d_status hj3d_probe_sel(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* probe, const hj3d_sel_pred* preds,
                            uint32_t npred, uint32_t flags, void* out_dev, uint64_t out_cap) {
-  if (!ctx || !t) return HJ3D_EINVAL;
   if (npred == 0) return hj3d_probe(ctx, t, probe, flags, out_dev, out_cap);
-  if (!rel_ok(probe)) return fail(ctx, HJ3D_EINVAL, "hj3d_probe_sel: invalid relation");
+  if (const hj3d_status st = probe_args_ok(ctx, "hj3d_probe_sel", t, probe, flags, out_dev, out_cap); st != HJ3D_OK)
+    return st;
   if (!sel_ok(probe, preds, npred)) return fail(ctx, HJ3D_EINVAL, "hj3d_probe_sel: invalid predicate");
-  if ((flags & HJ3D_PROBE_EMIT) && !out_dev && out_cap) return fail(ctx, HJ3D_EINVAL, "hj3d_probe_sel: EMIT without buffer");
-  if ((flags & HJ3D_PROBE_UNNEST) && t->desc.kind != HJ3D_NESTED)
-    return fail(ctx, HJ3D_EINVAL, "hj3d_probe_sel: UNNEST needs a nested table");
-  if (!mainref_ok(t, flags))
-    return fail(ctx, HJ3D_EINVAL, "hj3d_probe_sel: MAINREF needs a nested table, EMIT and no UNNEST");
   if (hipError_t re = resolve(ctx, t); re != hipSuccess) return from_hip(ctx, re, "hj3d_probe_sel");
+  const bool dense = dense_output(t, flags);
   const bool chain_radix = t->desc.kind == HJ3D_CHAIN && radix_probe_applicable(ctx, t, probe->n);
   const bool nested_radix = t->desc.kind == HJ3D_NESTED && radix_nested_applicable(ctx, t, probe->n);
   if (!ctx->sel_unfused && pk_probe_applicable(ctx, t, probe->n, flags)) {
@@ -706,7 +739,7 @@ hj3d_status hj3d_probe_sel(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* p
     const SelArgs a = sel_args(preds, npred);
     hipError_t e = pk_probe(ctx, t, *probe, flags, out_dev, out_cap, ctx->res.as<uint64_t>(), ctx->stream, &a);
     if (e != hipErrorNotSupported) {
-      note_probe(ctx, t, probe->n, flags, out_cap);
+      note_probe(ctx, dense, flags, probe->n, out_cap);
       return from_hip(ctx, e, "hj3d_probe_sel");
     }
   }
@@ -719,9 +752,9 @@ hj3d_status hj3d_probe_sel(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* p
     if (e == hipSuccess)
       e = chain_radix ? radix_probe(ctx, t, *probe, flags, out_dev, out_cap, res, ctx->stream, &a)
                       : radix_nested_probe(ctx, t, *probe, flags, out_dev, out_cap, res, ctx->stream, &a);
-    if (e == hipSuccess) e = out_check(ctx, t, flags, out_cap);
+    if (e == hipSuccess) e = out_check(ctx, dense, flags, out_cap);
     if (e != hipErrorNotSupported) {
-      note_probe(ctx, t, probe->n, flags, out_cap);
+      note_probe(ctx, dense, flags, probe->n, out_cap);
       return from_hip(ctx, e, "hj3d_probe_sel");
     }
   }
@@ -740,21 +773,10 @@ hj3d_status hj3d_probe_sel(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* p
 
 hj3d_status hj3d_probe_result(hj3d_ctx* ctx, hj3d_probe_res* out) {
   if (!ctx || !out) return HJ3D_EINVAL;
-  uint64_t h[kResFields], gw = 0;
-  hipError_t e = hipMemcpyAsync(h, ctx->res.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = gbar_copy(ctx, &gw);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) return from_hip(ctx, e, "hj3d_probe_result");
-  if (const hj3d_status gs = gbar_check(ctx, gw); gs != HJ3D_OK) return gs;
-  out->n_probe = h[0];
-  out->n_matched = h[1];
-  out->n_out = h[2];
-  out->n_cmps = h[3];
-  out->sum_a = h[4];
-  out->sum_b = h[5];
-  out->sum_c = h[6];
-  out->sum_h = h[7];
-  out->xor_h = h[8];
+  uint64_t h[kResFields];
+  if (const hj3d_status st = read_result(ctx, "hj3d_probe_result", h); st != HJ3D_OK) return st;
+  static_assert(sizeof(hj3d_probe_res) == kProbeFields * sizeof(uint64_t), "probe result layout");
+  std::memcpy(out, h, sizeof(hj3d_probe_res));
   const bool ovf = ctx->res_dense ? ctx->res_overflow : h[kResOvf] != 0;
   if ((ctx->res_flags & HJ3D_PROBE_EMIT) && ovf) return fail(ctx, HJ3D_EOVERFLOW, "hj3d_probe: output buffer too small");
   return HJ3D_OK;
@@ -765,7 +787,7 @@ hj3d_status hj3d_probe2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* t
   if (!ctx || !ts || !tt) return HJ3D_EINVAL;
   if (!rel_ok(probe)) return fail(ctx, HJ3D_EINVAL, "hj3d_probe2: invalid relation");
   if (ts->desc.kind != tt->desc.kind) return fail(ctx, HJ3D_EINVAL, "hj3d_probe2: both tables must be of one kind");
-  if ((flags & HJ3D_PROBE_EMIT) && !out_dev && out_cap) return fail(ctx, HJ3D_EINVAL, "hj3d_probe2: EMIT without buffer");
+  if (const hj3d_status st = emit_buffer_ok(ctx, "hj3d_probe2", flags, out_dev, out_cap); st != HJ3D_OK) return st;
   if ((flags & HJ3D_PROBE_EMIT) && (flags & HJ3D_PROBE_ACCUMULATE))
     return fail(ctx, HJ3D_EINVAL, "hj3d_probe2: EMIT with ACCUMULATE (the strand has no accumulate form)");
   if (hipError_t re = resolve(ctx, ts); re != hipSuccess) return from_hip(ctx, re, "hj3d_probe2");
@@ -777,20 +799,14 @@ hj3d_status hj3d_probe2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* t
     PhaseTimer tk(ctx, HJ3D_T_PROBE_KERNEL);
     e = probe2(ctx, ts, tt, *probe, flags, out_dev, out_cap, res, ctx->stream);  // (clears res itself)
   }
-  // remember what the overflow check needs (hj3d_probe2_result)
-  ctx->res2_flags = flags;
-  ctx->res2_cap = (flags & HJ3D_PROBE_EMIT) ? out_cap : ~0ull;
+  note_probe2(ctx, flags, out_cap);
   return from_hip(ctx, e, "hj3d_probe2");
 }
 
 hj3d_status hj3d_probe2_result(hj3d_ctx* ctx, hj3d_probe2_res* out) {
   if (!ctx || !out) return HJ3D_EINVAL;
-  uint64_t h[kResFields], gw = 0;
-  hipError_t e = hipMemcpyAsync(h, ctx->res.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = gbar_copy(ctx, &gw);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) return from_hip(ctx, e, "hj3d_probe2_result");
-  if (const hj3d_status gs = gbar_check(ctx, gw); gs != HJ3D_OK) return gs;
+  uint64_t h[kResFields];
+  if (const hj3d_status st = read_result(ctx, "hj3d_probe2_result", h); st != HJ3D_OK) return st;
   static_assert(sizeof(hj3d_probe2_res) == 12 * sizeof(uint64_t), "probe2 result layout");
   std::memcpy(out, h, sizeof(hj3d_probe2_res));
   // c_top counts every triple; those past the buffer were dropped
@@ -802,33 +818,25 @@ hj3d_status hj3d_probe2_result(hj3d_ctx* ctx, hj3d_probe2_res* out) {
 hj3d_status hj3d_unnest(hj3d_ctx* ctx, const hj3d_table* t, const void* nested_dev, uint64_t n, uint32_t flags,
                         void* out_dev, uint64_t out_cap) {
   if (!ctx || !t) return HJ3D_EINVAL;
-  if (flags & ~(HJ3D_PROBE_EMIT | HJ3D_PROBE_CHECKSUM)) return fail(ctx, HJ3D_EINVAL, "hj3d_unnest: flags other than EMIT, CHECKSUM");
+  if (const hj3d_status st = unnest_flags_ok(ctx, "hj3d_unnest", flags); st != HJ3D_OK) return st;
   if (t->desc.kind != HJ3D_NESTED) return fail(ctx, HJ3D_EINVAL, "hj3d_unnest: needs a nested table");
   if ((n && !nested_dev) || n >= (1ull << 32)) return fail(ctx, HJ3D_EINVAL, "hj3d_unnest: invalid input");
-  if ((flags & HJ3D_PROBE_EMIT) && !out_dev && out_cap) return fail(ctx, HJ3D_EINVAL, "hj3d_unnest: EMIT without buffer");
+  if (const hj3d_status st = emit_buffer_ok(ctx, "hj3d_unnest", flags, out_dev, out_cap); st != HJ3D_OK) return st;
   if (hipError_t re = resolve(ctx, t); re != hipSuccess) return from_hip(ctx, re, "hj3d_unnest");
   PhaseTimer tm(ctx, HJ3D_T_PROBE);
   uint64_t* res = ctx->res.as<uint64_t>();
   hipError_t e = hipMemsetAsync(res, 0, kResFields * sizeof(uint64_t), ctx->stream);
   if (e == hipSuccess) e = unnest_pairs(ctx, t, nested_dev, n, flags, out_dev, out_cap, res, ctx->stream);
-  // the non-dense overflow convention (out_check): n_out against the capacity, on the stream
-  if (e == hipSuccess && (flags & HJ3D_PROBE_EMIT)) {
-    hipLaunchKernelGGL(k_out_overflow, dim3(1), dim3(64), 0, ctx->stream, res, out_cap);
-    e = hipGetLastError();
-  }
-  ctx->res_flags = flags;
-  ctx->res_dense = false;
-  ctx->res_cap = (flags & HJ3D_PROBE_EMIT) ? out_cap : ~0ull;
-  ctx->res_nprobe = n;
-  ctx->res_overflow = false;
-  ctx->res_accumulated = false;
+  // the non-dense overflow convention: n_out against the capacity, on the stream
+  if (e == hipSuccess) e = out_check(ctx, false, flags, out_cap);
+  note_probe(ctx, false, flags, n, out_cap);
   return from_hip(ctx, e, "hj3d_unnest");
 }
 
 hj3d_status hj3d_unnest2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const void* nested_dev,
                          uint64_t n, uint32_t flags, void* out_dev, uint64_t out_cap) {
   if (!ctx || !ts || !tt) return HJ3D_EINVAL;
-  if (flags & ~(HJ3D_PROBE_EMIT | HJ3D_PROBE_CHECKSUM)) return fail(ctx, HJ3D_EINVAL, "hj3d_unnest2: flags other than EMIT, CHECKSUM");
+  if (const hj3d_status st = unnest_flags_ok(ctx, "hj3d_unnest2", flags); st != HJ3D_OK) return st;
   if (ts->desc.kind != HJ3D_NESTED || tt->desc.kind != HJ3D_NESTED)
     return fail(ctx, HJ3D_EINVAL, "hj3d_unnest2: needs two nested tables");
   if ((n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32))
@@ -840,8 +848,7 @@ hj3d_status hj3d_unnest2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* 
   PhaseTimer tm(ctx, HJ3D_T_PROBE);
   const hipError_t e =
       unnest_triples(ctx, ts, tt, nested_dev, n, flags, out_dev, out_cap, ctx->res.as<uint64_t>(), ctx->stream);
-  ctx->res2_flags = flags;
-  ctx->res2_cap = (flags & HJ3D_PROBE_EMIT) ? out_cap : ~0ull;
+  note_probe2(ctx, flags, out_cap);
   return from_hip(ctx, e, "hj3d_unnest2");
 }
 
@@ -928,22 +935,19 @@ hj3d_status hj3d_select(hj3d_ctx* ctx, const hj3d_rel* rel, const hj3d_sel_pred*
 
 hj3d_status hj3d_gen_keys(hj3d_ctx* ctx, void* tuples, uint64_t n, uint32_t stride, uint32_t key_off,
                           uint64_t row_base, uint64_t n_keys, uint64_t seed) {
-  if (!ctx || (n && !tuples) || stride == 0 || (stride & 3) || (key_off & 3) || key_off + 4 > stride)
-    return HJ3D_EINVAL;
+  if (!ctx || !tuples_ok(n, tuples, stride, key_off)) return HJ3D_EINVAL;
   return from_hip(ctx, gen_keys(tuples, n, stride, key_off, row_base, n_keys, seed, ctx->stream), "hj3d_gen_keys");
 }
 
 hj3d_status hj3d_gen_fk(hj3d_ctx* ctx, void* tuples, uint64_t n, uint32_t stride, uint32_t key_off,
                         uint64_t row_base, uint32_t fk_max, uint64_t seed) {
-  if (!ctx || (n && !tuples) || stride == 0 || (stride & 3) || (key_off & 3) || key_off + 4 > stride || fk_max == 0)
-    return HJ3D_EINVAL;
+  if (!ctx || !tuples_ok(n, tuples, stride, key_off) || fk_max == 0) return HJ3D_EINVAL;
   return from_hip(ctx, gen_fk(tuples, n, stride, key_off, row_base, fk_max, seed, ctx->stream), "hj3d_gen_fk");
 }
 
 hj3d_status hj3d_gen_zipf(hj3d_ctx* ctx, void* tuples, uint64_t n, uint32_t stride, uint32_t key_off,
                           uint64_t row_base, uint32_t fk_max, double theta, uint64_t seed) {
-  if (!ctx || (n && !tuples) || stride == 0 || (stride & 3) || (key_off & 3) || key_off + 4 > stride || fk_max == 0 ||
-      !(theta > 0.0) || theta > 10.0)
+  if (!ctx || !tuples_ok(n, tuples, stride, key_off) || fk_max == 0 || !(theta > 0.0) || theta > 10.0)
     return HJ3D_EINVAL;
   return from_hip(ctx, gen_zipf(tuples, n, stride, key_off, row_base, fk_max, theta, seed, ctx->stream),
                   "hj3d_gen_zipf");

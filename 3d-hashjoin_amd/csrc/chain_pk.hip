@@ -1106,85 +1106,117 @@ PkPlan pk_plan(const hj3d_ctx* ctx, uint32_t nbl, uint64_t n_build) {
   return pl;
 }
 
-hipError_t pk_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, uint32_t flags, void* out, uint64_t out_cap,
-                    uint64_t* res, hipStream_t s, const SelArgs* sel) {
+static uint32_t bits(uint64_t x) {
+  uint32_t b = 0;
+  while (x) {
+    ++b;
+    x >>= 1;
+  }
+  return b;
+}
+
+// The packed partitioner's layout for n tuples into P slices of W buckets, C slices per coarse range
+// of the first level: pass 1 (k_pk_part) writes G x P1 regions of cap pairs and, with `two`, pass 2
+// (k_pk_split) S2 x P fine regions of cap2. The pointers are the scratch arrays after their ensures
+// (fine / fcnt only with `two`, ps only with `sums`).
+struct PkLayout {
+  uint32_t qbits = 0, ntiles = 0, G = 0, S2 = 0;
+  uint64_t cap = 0, cap2 = 0, nreg = 0, nreg2 = 0;
+  PkGeom pk1{}, pk{};
+  uint2 *region = nullptr, *ovf = nullptr, *fine = nullptr;
+  uint32_t *counts = nullptr, *fcnt = nullptr, *ps = nullptr;
+  uint64_t* ctl = nullptr;
+};
+
+// hipErrorNotSupported: the packed word or a region array beyond its limits
+static hipError_t pk_layout(hj3d_ctx* ctx, const hj3d_table* t, uint64_t n, uint32_t W, uint32_t P, uint32_t C, bool two,
+                            bool sums, PkLayout* L) {
   hipError_t e;
   const uint32_t nbl = t->nb_local, nb = uint32_t(t->desc.num_buckets);
-  const PkPlan pl = pk_plan(ctx, nbl, t->n_build);
-  const bool two = pl.C > 1;
-  if (pl.C > kSpMaxC) return hipErrorNotSupported;
+  const uint32_t W1 = W * C, P1 = (nbl + W1 - 1) / W1;
   // the packed word: bucket in the (first-level) slice and the quotient h / NB (bits of its max)
-  auto bits = [](uint64_t x) { uint32_t b = 0; while (x) { ++b; x >>= 1; } return b; };
-  const uint32_t qbits = bits(0xFFFFFFFFull / nb), wbits = bits(pl.W1 - 1);
-  if (qbits + wbits > 32) return hipErrorNotSupported;
-  SelRange sr{};
-  if (sel && !SelRange::from(*sel, &sr)) return hipErrorNotSupported;
-  const uint32_t ntiles = uint32_t((r.n + kPkTile - 1) / kPkTile);
-  const uint32_t G = ntiles < uint32_t(ctx->num_cus) ? ntiles : uint32_t(ctx->num_cus);
+  const uint32_t qbits = L->qbits = bits(0xFFFFFFFFull / nb);
+  if (qbits + bits(W1 - 1) > 32) return hipErrorNotSupported;
+  const uint32_t ntiles = L->ntiles = uint32_t((n + kPkTile - 1) / kPkTile);
+  const uint32_t G = L->G = ntiles < uint32_t(ctx->num_cus) ? ntiles : uint32_t(ctx->num_cus);
   // region capacity: expected pairs per (workgroup, slice) + 8 sigma + slack, whole segments
-  auto capacity = [](double ex) {
-    uint64_t c = uint64_t(ex + 8.0 * std::sqrt(ex) + 32.0);
-    return (c + kPkSeg - 1) / kPkSeg * kPkSeg;
-  };
   const uint64_t per_g = uint64_t((ntiles + G - 1) / G) * kPkTile;
-  const uint64_t cap = capacity(double(per_g < r.n ? per_g : r.n) / pl.P1);
-  const uint64_t nreg = uint64_t(G) * pl.P1;
+  const uint64_t cap = L->cap = region_capacity(double(per_g < n ? per_g : n) / P1, kPkSeg);
+  const uint64_t nreg = L->nreg = uint64_t(G) * P1;
   if (nreg * cap >= (1ull << 31)) return hipErrorNotSupported;
   // second level: S2 workgroups per coarse range, each writing one fine region per slice
-  const uint32_t S2 = two ? (G < 16u ? G : 16u) : 0u;
+  const uint32_t S2 = L->S2 = two ? (G < 16u ? G : 16u) : 0u;
   // a fine region gathers the pass-1 regions of ceil(G / S2) workgroups at most (G need not be a
   // multiple of S2): its expected pairs are that many workgroups' share of the slice
-  const double per_gp = double(per_g < r.n ? per_g : r.n) / pl.P;
-  const uint64_t cap2 = two ? capacity(per_gp * double((G + S2 - 1) / S2)) : 0;
-  const uint64_t nreg2 = uint64_t(S2) * pl.P;
+  const double per_gp = double(per_g < n ? per_g : n) / P;
+  const uint64_t cap2 = L->cap2 = two ? region_capacity(per_gp * double((G + S2 - 1) / S2), kPkSeg) : 0;
+  const uint64_t nreg2 = L->nreg2 = uint64_t(S2) * P;
   if (two && nreg2 * cap2 >= (1ull << 31)) return hipErrorNotSupported;
   if ((e = ctx->scratch[kScrPairs].ensure(nreg * cap * sizeof(uint2))) != hipSuccess) return e;
   if ((e = ctx->scratch[kScrPHist].ensure(nreg * sizeof(uint32_t))) != hipSuccess) return e;
-  if ((e = ctx->scratch[kScrSortV].ensure(r.n * sizeof(uint2))) != hipSuccess) return e;
+  if ((e = ctx->scratch[kScrSortV].ensure(n * sizeof(uint2))) != hipSuccess) return e;
   if (two) {
     if ((e = ctx->scratch[kScrPk2].ensure(nreg2 * cap2 * sizeof(uint2))) != hipSuccess) return e;
     if ((e = ctx->scratch[kScrPk2Cnt].ensure(nreg2 * sizeof(uint32_t))) != hipSuccess) return e;
   }
+  if (sums && (e = ctx->scratch[kScrPStart].ensure((uint64_t(P) + 1) * sizeof(uint32_t))) != hipSuccess) return e;
+  if ((e = ctx->ensure_ctl()) != hipSuccess) return e;
+  auto geom = [&](uint32_t w, uint32_t p) {
+    PkGeom g;
+    g.dnb = FastDiv32::make(nb);
+    g.dw = w >= 2 ? FastDiv32::make(w) : FastDiv32{};
+    g.nb = nb;
+    g.lo = uint32_t(t->desc.bucket_lo);
+    g.nbl = nbl;
+    g.W = w;
+    g.P = p;
+    g.qbits = qbits;
+    g.qmask = qbits >= 32 ? 0xFFFFFFFFu : ((1u << qbits) - 1);
+    return g;
+  };
+  L->pk1 = geom(W1, P1);
+  L->pk = geom(W, P);
+  L->region = ctx->scratch[kScrPairs].as<uint2>();
+  L->counts = ctx->scratch[kScrPHist].as<uint32_t>();
+  L->ovf = ctx->scratch[kScrSortV].as<uint2>();
+  L->fine = two ? ctx->scratch[kScrPk2].as<uint2>() : nullptr;
+  L->fcnt = two ? ctx->scratch[kScrPk2Cnt].as<uint32_t>() : nullptr;
+  L->ps = sums ? ctx->scratch[kScrPStart].as<uint32_t>() : nullptr;
+  L->ctl = ctx->ctl.as<uint64_t>();
+  return hipSuccess;
+}
+
+hipError_t pk_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, uint32_t flags, void* out, uint64_t out_cap,
+                    uint64_t* res, hipStream_t s, const SelArgs* sel) {
+  hipError_t e;
+  const PkPlan pl = pk_plan(ctx, t->nb_local, t->n_build);
+  const bool two = pl.C > 1;
+  if (pl.C > kSpMaxC) return hipErrorNotSupported;
+  SelRange sr{};
+  if (sel && !SelRange::from(*sel, &sr)) return hipErrorNotSupported;
+  PkLayout L;
+  if ((e = pk_layout(ctx, t, r.n, pl.W, pl.P, pl.C, two, false, &L)) != hipSuccess) return e;
   const uint32_t want_blocks = uint32_t(ctx->num_cus) * 2;
-  const uint32_t Gp = two ? S2 : G;  // regions per slice that the probe walks
+  const uint32_t Gp = two ? L.S2 : L.G;  // regions per slice that the probe walks
   uint32_t splits = pl.P < want_blocks ? (want_blocks + pl.P - 1) / pl.P : 1u;
   if (splits > Gp) splits = Gp;
   const uint32_t nblocks = pl.P * splits;
   if ((e = ctx->scratch[kScrPartial].ensure(uint64_t(nblocks) * kProbeFields * sizeof(uint64_t))) != hipSuccess)
     return e;
-  if ((e = ctx->ensure_ctl()) != hipSuccess) return e;
-  auto geom = [&](uint32_t W, uint32_t P) {
-    PkGeom g;
-    g.dnb = FastDiv32::make(nb);
-    g.dw = W >= 2 ? FastDiv32::make(W) : FastDiv32{};
-    g.nb = nb;
-    g.lo = uint32_t(t->desc.bucket_lo);
-    g.nbl = nbl;
-    g.W = W;
-    g.P = P;
-    g.qbits = qbits;
-    g.qmask = qbits >= 32 ? 0xFFFFFFFFu : ((1u << qbits) - 1);
-    return g;
-  };
-  const PkGeom pk1 = geom(pl.W1, pl.P1), pk = geom(pl.W, pl.P);
-  uint2* region = ctx->scratch[kScrPairs].as<uint2>();
-  uint32_t* counts = ctx->scratch[kScrPHist].as<uint32_t>();
-  uint2* ovf = ctx->scratch[kScrSortV].as<uint2>();
-  uint64_t* ctl = ctx->ctl.as<uint64_t>();
   const RelView v = view_of(r);
   const bool imp = r.row_off == HJ3D_ROW_IMPLICIT;
   const uint32_t slim = ctx->pk_stage ? (ctx->pk_stage < kPkStage ? ctx->pk_stage : kPkStage) : kPkStage;
   {
     KernelSpan tm(ctx, HJ3D_T_SCATTER);
-    const uint32_t c32 = uint32_t(cap);
+    const uint32_t c32 = uint32_t(L.cap);
     // (one level beyond 1024 slices: two slices per partitioning thread)
     const uint32_t slim2 = slim < kPkStage2 ? slim : kPkStage2;
 #define HJ3D_PKP_LAUNCH(IMP, SEL)                                                                                   \
   if (pl.P1 > uint32_t(kPkBlock))                                                                                   \
-    tm.launch(k_pk_part<IMP, SEL, 2>, dim3(G), dim3(kPkBlock), s, v, pk1, ntiles, c32, region, counts, ovf, ctl, sr, \
+    tm.launch(k_pk_part<IMP, SEL, 2>, dim3(L.G), dim3(kPkBlock), s, v, L.pk1, L.ntiles, c32, L.region, L.counts, L.ovf, L.ctl, sr, \
               slim2);                                                                                               \
   else                                                                                                              \
-    tm.launch(k_pk_part<IMP, SEL, 1>, dim3(G), dim3(kPkBlock), s, v, pk1, ntiles, c32, region, counts, ovf, ctl, sr, slim);
+    tm.launch(k_pk_part<IMP, SEL, 1>, dim3(L.G), dim3(kPkBlock), s, v, L.pk1, L.ntiles, c32, L.region, L.counts, L.ovf, L.ctl, sr, slim);
     if (sel) {
       if (imp) HJ3D_PKP_LAUNCH(true, true)
       else HJ3D_PKP_LAUNCH(false, true)
@@ -1195,20 +1227,18 @@ hipError_t pk_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, uint3
 #undef HJ3D_PKP_LAUNCH
   }
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  const uint2* pregion = region;
-  const uint32_t* pcounts = counts;
-  uint32_t pcap = uint32_t(cap);
+  const uint2* pregion = L.region;
+  const uint32_t* pcounts = L.counts;
+  uint32_t pcap = uint32_t(L.cap);
   if (two) {
-    uint2* fine = ctx->scratch[kScrPk2].as<uint2>();
-    uint32_t* fcnt = ctx->scratch[kScrPk2Cnt].as<uint32_t>();
     KernelSpan ts(ctx, HJ3D_T_HIST);
-    ts.launch(k_pk_split, dim3(pl.P1 * S2), dim3(kSpBlock), s, static_cast<const uint2*>(region),
-              static_cast<const uint32_t*>(counts), G, pl.P1, uint32_t(cap), S2, pk, pl.C, bits(pl.C - 1),
-              uint32_t(cap2), fine, fcnt, ovf, ctl);
+    ts.launch(k_pk_split, dim3(pl.P1 * L.S2), dim3(kSpBlock), s, static_cast<const uint2*>(L.region),
+              static_cast<const uint32_t*>(L.counts), L.G, pl.P1, uint32_t(L.cap), L.S2, L.pk, pl.C, bits(pl.C - 1),
+              uint32_t(L.cap2), L.fine, L.fcnt, L.ovf, L.ctl);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    pregion = fine;
-    pcounts = fcnt;
-    pcap = uint32_t(cap2);
+    pregion = L.fine;
+    pcounts = L.fcnt;
+    pcap = uint32_t(L.cap2);
   }
   const bool emit = (flags & HJ3D_PROBE_EMIT) && out;
   const bool ck = flags & HJ3D_PROBE_CHECKSUM;
@@ -1224,8 +1254,8 @@ hipError_t pk_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, uint3
     KernelSpan tk(ctx, HJ3D_T_PROBE_KERNEL);
 #define HJ3D_PK_LAUNCH(K, MODE, CK)                                                                                  \
   tk.launch(k_pk_probe<K, MODE, CK>, dim3(nblocks), dim3(kPkBlock), s, pregion, pcounts, Gp, pcap,              \
-                     splits, flat, t->off.as<const uint32_t>(), t->ent.as<const uint2>(), pk, t->fm, o, out_cap, ovf, \
-                     ctl, partials, res, acc)
+                     splits, flat, t->off.as<const uint32_t>(), t->ent.as<const uint2>(), L.pk, t->fm, o, out_cap,   \
+                     L.ovf, L.ctl, partials, res, acc)
 #define HJ3D_PK_LAUNCH_K(MODE, CK)               \
   switch (items) {                               \
     case 5: HJ3D_PK_LAUNCH(5, MODE, CK); break;  \
@@ -1255,82 +1285,38 @@ hipError_t pk_slices(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, uint
   const uint32_t P = (nbl + W - 1) / W;
   const uint32_t C = (P + kPkBlock - 1) / kPkBlock;
   if (C > kSpMaxC) return hipErrorNotSupported;
-  const uint32_t W1 = W * C, P1 = (nbl + W1 - 1) / W1;
-  auto bits = [](uint64_t x) { uint32_t b = 0; while (x) { ++b; x >>= 1; } return b; };
-  const uint32_t qbits = bits(0xFFFFFFFFull / nb);
-  // the packed word holds the bucket inside the coarse range (and, after the split, inside the
-  // slice, whose width W must also fit, for the nested build's empty marker W << qbits)
-  if (qbits + bits(W1 - 1) > 32 || qbits + bits(W) > 32) return hipErrorNotSupported;
-  const uint32_t ntiles = uint32_t((r.n + kPkTile - 1) / kPkTile);
-  const uint32_t G = ntiles < uint32_t(ctx->num_cus) ? ntiles : uint32_t(ctx->num_cus);
-  auto capacity = [](double ex) {
-    uint64_t c = uint64_t(ex + 8.0 * std::sqrt(ex) + 32.0);
-    return (c + kPkSeg - 1) / kPkSeg * kPkSeg;
-  };
-  const uint64_t per_g = uint64_t((ntiles + G - 1) / G) * kPkTile;
-  const uint64_t cap = capacity(double(per_g < r.n ? per_g : r.n) / P1);
-  const uint64_t nreg = uint64_t(G) * P1;
-  const uint32_t S2 = G < 16u ? G : 16u;
-  // a fine region gathers the pass-1 regions of ceil(G / S2) workgroups at most (G need not be a
-  // multiple of S2): its expected pairs are that many workgroups' share of the slice
-  const double per_gp = double(per_g < r.n ? per_g : r.n) / P;
-  const uint64_t cap2 = capacity(per_gp * double((G + S2 - 1) / S2));
-  const uint64_t nreg2 = uint64_t(S2) * P;
-  if (nreg * cap >= (1ull << 31) || nreg2 * cap2 >= (1ull << 31)) return hipErrorNotSupported;
-  if ((e = ctx->scratch[kScrPairs].ensure(nreg * cap * sizeof(uint2))) != hipSuccess) return e;
-  if ((e = ctx->scratch[kScrPHist].ensure(nreg * sizeof(uint32_t))) != hipSuccess) return e;
-  if ((e = ctx->scratch[kScrSortV].ensure(r.n * sizeof(uint2))) != hipSuccess) return e;
-  if ((e = ctx->scratch[kScrPk2].ensure(nreg2 * cap2 * sizeof(uint2))) != hipSuccess) return e;
-  if ((e = ctx->scratch[kScrPk2Cnt].ensure(nreg2 * sizeof(uint32_t))) != hipSuccess) return e;
-  if (sums && (e = ctx->scratch[kScrPStart].ensure((uint64_t(P) + 1) * sizeof(uint32_t))) != hipSuccess) return e;
-  if ((e = ctx->ensure_ctl()) != hipSuccess) return e;
-  auto geom = [&](uint32_t w, uint32_t p) {
-    PkGeom g;
-    g.dnb = FastDiv32::make(nb);
-    g.dw = FastDiv32::make(w);
-    g.nb = nb;
-    g.lo = uint32_t(t->desc.bucket_lo);
-    g.nbl = nbl;
-    g.W = w;
-    g.P = p;
-    g.qbits = qbits;
-    g.qmask = qbits >= 32 ? 0xFFFFFFFFu : ((1u << qbits) - 1);
-    return g;
-  };
-  const PkGeom pk1 = geom(W1, P1), pk = geom(W, P);
-  uint2* region = ctx->scratch[kScrPairs].as<uint2>();
-  uint32_t* counts = ctx->scratch[kScrPHist].as<uint32_t>();
-  uint2* ovf = ctx->scratch[kScrSortV].as<uint2>();
-  uint2* fine = ctx->scratch[kScrPk2].as<uint2>();
-  uint32_t* fcnt = ctx->scratch[kScrPk2Cnt].as<uint32_t>();
-  uint32_t* ps = sums ? ctx->scratch[kScrPStart].as<uint32_t>() : nullptr;
-  uint64_t* ctl = ctx->ctl.as<uint64_t>();
+  // the packed word holds the bucket inside the coarse range (pk_layout) and, after the split, inside
+  // the slice, whose width W must also fit, for the nested build's empty marker W << qbits
+  if (bits(0xFFFFFFFFull / nb) + bits(W) > 32) return hipErrorNotSupported;
+  PkLayout L;
+  if ((e = pk_layout(ctx, t, r.n, W, P, C, true, sums, &L)) != hipSuccess) return e;
   const RelView v = view_of(r);
   SelRange sr{};
   if (r.row_off == HJ3D_ROW_IMPLICIT)
-    hipLaunchKernelGGL((k_pk_part<true, false, 1>), dim3(G), dim3(kPkBlock), 0, s, v, pk1, ntiles, uint32_t(cap), region,
-                       counts, ovf, ctl, sr, kPkStage);
+    hipLaunchKernelGGL((k_pk_part<true, false, 1>), dim3(L.G), dim3(kPkBlock), 0, s, v, L.pk1, L.ntiles, uint32_t(L.cap),
+                       L.region, L.counts, L.ovf, L.ctl, sr, kPkStage);
   else
-    hipLaunchKernelGGL((k_pk_part<false, false, 1>), dim3(G), dim3(kPkBlock), 0, s, v, pk1, ntiles, uint32_t(cap), region,
-                       counts, ovf, ctl, sr, kPkStage);
+    hipLaunchKernelGGL((k_pk_part<false, false, 1>), dim3(L.G), dim3(kPkBlock), 0, s, v, L.pk1, L.ntiles, uint32_t(L.cap),
+                       L.region, L.counts, L.ovf, L.ctl, sr, kPkStage);
   // (C = 1: the split only regroups each slice's G regions into S2)
-  hipLaunchKernelGGL(k_pk_split, dim3(P1 * S2), dim3(kSpBlock), 0, s, static_cast<const uint2*>(region),
-                     static_cast<const uint32_t*>(counts), G, P1, uint32_t(cap), S2, pk, C, bits(C - 1), uint32_t(cap2),
-                     fine, fcnt, ovf, ctl);
+  hipLaunchKernelGGL(k_pk_split, dim3(L.pk1.P * L.S2), dim3(kSpBlock), 0, s, static_cast<const uint2*>(L.region),
+                     static_cast<const uint32_t*>(L.counts), L.G, L.pk1.P, uint32_t(L.cap), L.S2, L.pk, C, bits(C - 1),
+                     uint32_t(L.cap2), L.fine, L.fcnt, L.ovf, L.ctl);
   if (sums) {
-    hipLaunchKernelGGL(k_pk_slice_sums, dim3((P + 255) / 256), dim3(256), 0, s, static_cast<const uint32_t*>(fcnt), S2, P, ps);
+    hipLaunchKernelGGL(k_pk_slice_sums, dim3((P + 255) / 256), dim3(256), 0, s, static_cast<const uint32_t*>(L.fcnt), L.S2,
+                       P, L.ps);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = exclusive_scan_u32(ctx, ps, ps, P, s)) != hipSuccess) return e;
+    if ((e = exclusive_scan_u32(ctx, L.ps, L.ps, P, s)) != hipSuccess) return e;
   }
-  o->pk = pk;
+  o->pk = L.pk;
   o->P = P;
-  o->S2 = S2;
-  o->cap2 = uint32_t(cap2);
-  o->fine = fine;
-  o->fcnt = fcnt;
-  o->ps = ps;
-  o->ovf = ovf;
-  o->novf = reinterpret_cast<const unsigned long long*>(ctl + kCtlNovf);
+  o->S2 = L.S2;
+  o->cap2 = uint32_t(L.cap2);
+  o->fine = L.fine;
+  o->fcnt = L.fcnt;
+  o->ps = L.ps;
+  o->ovf = L.ovf;
+  o->novf = reinterpret_cast<const unsigned long long*>(L.ctl + kCtlNovf);
   return hipGetLastError();
 }
 

@@ -531,7 +531,7 @@ hipError_t probe2_on(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, 
       const double fill = double(ts->n_mains + tt->n_mains) / double(ts->nb_local);
       ProbeParts pp;
       // no output: the regions' output slots are not needed
-      e = radix_partition_probe(ctx, ts, r, uint32_t(0.8 * kProbeLdsWords / (2.0 + 4.0 * fill)), &pp, s, nullptr,
+      e = radix_partition_probe(ctx, ts, r, uint32_t(kProbeWFrac * kProbeLdsWords / (2.0 + 4.0 * fill)), &pp, s, nullptr,
                                 nullptr, false, &z);
       if (e == hipSuccess) {
         const uint32_t nblocks = pp.P * pp.splits;

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -60,6 +61,19 @@ struct DevBuf {
 // comm.hip: false (and why) when two HIP runtimes are mapped into the process
 bool runtime_check(std::string* msg);
 
+// Scratch slot ids in hj3d_ctx::scratch.
+enum ScratchSlot {
+  kScrScan = 0, kScrSlot = 1, kScrSortK = 2, kScrSortV = 3, kScrA = 4, kScrB = 5, kScrC = 6, kScrD = 7,
+  kScrPairs = 8,    // radix-partitioned (hash, row) pairs
+  kScrPHist = 9,    // radix partition histograms / offsets
+  kScrPartial = 10, // per-block result partials
+  kScrPStart = 11,  // partition starts of the probe side
+  kScrPk2 = 12,     // packed probe, second partition level: fine regions
+  kScrPk2Cnt = 13,  // and their pair counts
+  kScrSink = 14,    // 1024 pairs: target of the stores of lanes without a pair (fixed store counts)
+  kScrSlots = 15
+};
+static_assert(kScrSink + 1 == kScrSlots, "kScrSlots counts the scratch slots");
 }  // namespace hj3d
 
 struct hj3d_comm_state;  // comm.hip: RCCL communicator, exchange stream, tickets
@@ -75,7 +89,7 @@ struct hj3d_ctx {
   int num_cus = 256;
   std::string last_error;
   // scratch arena slots (see api for their use)
-  hj3d::DevBuf scratch[15];
+  hj3d::DevBuf scratch[hj3d::kScrSlots];
   hj3d::DevBuf res;       // device result slot (u64 fields) for probe / probe2
   hj3d::DevBuf misc;      // small device reductions (statistics)
   uint32_t res_flags = 0;     // flags of the last probe (overflow check in hj3d_probe_result)
@@ -165,7 +179,7 @@ struct hj3d_table {
                           // fused-partition barrier timeout tag (chaining)}
   // chaining tables built by the fused partition: its launch tag (0: none). Never set on a nested
   // table (partition_pairs takes the fused form for HJ3D_CHAIN only), and cleared wherever a table's
-  // content is replaced: build_one, hj3d_build_many, hj3d_table_clear, table_resolve's sort fallback
+  // content is replaced: begin_build (every build), hj3d_table_clear, table_resolve's sort fallback
   uint64_t gbar_tag = 0;
 };
 
@@ -322,6 +336,12 @@ struct ProbeParts {
   const uint2* ovf = nullptr;
   const unsigned long long* novf = nullptr;
 };
+// Pairs a partition region holds: the expected number + 8 sigma + slack, in whole segments of
+// `segment` pairs (the probe-side partitioners of radix.hip and chain_pk.hip).
+inline uint64_t region_capacity(double expected, uint32_t segment) {
+  const uint64_t c = uint64_t(expected + 8.0 * std::sqrt(expected) + 32.0);
+  return (c + segment - 1) / segment * segment;
+}
 // slots = false: the caller never writes output (the dense output slots of the regions, a
 // transpose + scan of the region counts, are not computed; pp->seg is then undefined)
 // also (optional): words the caller needs zeroed before the strand, cleared by the same launch as
@@ -444,19 +464,6 @@ hipError_t expected_fk_join_gen(hj3d_ctx* ctx, const hj3d_rel& probe, uint64_t n
 // api.cpp: completes a nested build whose counts are still in flight (reads them; runs the sort
 // build when the aggregation build gave up). Every use of a table's content calls it first.
 hipError_t table_resolve(hj3d_ctx* ctx, hj3d_table* t);
-
-// Scratch slot ids in hj3d_ctx::scratch.
-enum ScratchSlot {
-  kScrScan = 0, kScrSlot = 1, kScrSortK = 2, kScrSortV = 3, kScrA = 4, kScrB = 5, kScrC = 6, kScrD = 7,
-  kScrPairs = 8,    // radix-partitioned (hash, row) pairs
-  kScrPHist = 9,    // radix partition histograms / offsets
-  kScrPartial = 10, // per-block result partials
-  kScrPStart = 11,  // partition starts of the probe side
-  kScrPk2 = 12,     // packed probe, second partition level: fine regions
-  kScrPk2Cnt = 13,  // and their pair counts
-  kScrSink = 14,    // 1024 pairs: target of the stores of lanes without a pair (fixed store counts)
-  kScrSlots = 15
-};
 
 // Per-block result partials: kernels store their block totals (block_store) to
 // partials[block * nf ...]; reduce_partials adds the column sums into res (stream-ordered).

@@ -738,6 +738,41 @@ hipError_t expand(hj3d_ctx* ctx, const SlotSrc& src, bool slots, int ck, uint64_
   return hipGetLastError();
 }
 
+// The materialised unnest's tail over n slots whose output counts are in cnt: scan, expansion, and the
+// light kernel's per-workgroup partials added to res where sums were folded (ck != 0). The callers
+// carve the slot arrays and the heavy list; hoff (kScrD) and the partials are sized here.
+hipError_t expand_slots(hj3d_ctx* ctx, const SlotSrc& src, bool slots, int ck, uint64_t n, uint64_t* cnt,
+                        const uint32_t* sub, uint2* out, uint64_t out_cap, uint32_t* heavy, uint32_t* nheavy,
+                        uint64_t* res, hipStream_t s) {
+  hipError_t e;
+  const uint32_t nblk = uint32_t((n + kBlock - 1) / kBlock);
+  if ((e = exclusive_scan_u64(ctx, cnt, cnt, n, s)) != hipSuccess) return e;
+  if ((e = ctx->scratch[kScrD].ensure((n + 2) * sizeof(uint64_t))) != hipSuccess) return e;  // hoff
+  if ((e = ctx->scratch[kScrPartial].ensure(uint64_t(nblk) * kProbeFields * sizeof(uint64_t))) != hipSuccess) return e;
+  uint64_t* partials = ctx->scratch[kScrPartial].as<uint64_t>();
+  if ((e = expand(ctx, src, slots, ck, n, cnt, sub, out, out_cap, heavy, nheavy, partials, res, s)) != hipSuccess)
+    return e;
+  return ck ? reduce_partials(partials, nblk, kProbeFields, 1, res, s) : hipSuccess;
+}
+
+// The probe kernels' MODE for a call's flags (EMIT counts only with a buffer), and the switch that
+// turns it into a template argument: f(std::integral_constant<int, mode>).
+int nested_mode(uint32_t flags, const void* out) {
+  const bool emit = (flags & HJ3D_PROBE_EMIT) && out;
+  if (flags & HJ3D_PROBE_UNNEST) return emit ? kCountUN : kAggUN;
+  return !emit ? kAggNU : (flags & HJ3D_PROBE_MAINREF) ? kDenseRef : kDenseNU;
+}
+template <typename F>
+void with_mode(int mode, F&& f) {
+  switch (mode) {
+    case kAggNU: f(std::integral_constant<int, kAggNU>{}); break;
+    case kDenseNU: f(std::integral_constant<int, kDenseNU>{}); break;
+    case kDenseRef: f(std::integral_constant<int, kDenseRef>{}); break;
+    case kAggUN: f(std::integral_constant<int, kAggUN>{}); break;
+    default: f(std::integral_constant<int, kCountUN>{}); break;
+  }
+}
+
 // hj3d_unnest's first pass: one slot per input pair {a, main_ref}, in the form the expansion takes
 // (output count, sub_off, a). A ref outside [0, n_mains) is skipped (0xFFFFFFFF = no match; a table
 // cleared or rebuilt smaller since the probe): count 0, and no main record is read for it.
@@ -770,30 +805,22 @@ hipError_t unnest_pairs(hj3d_ctx* ctx, const hj3d_table* t, const void* in, uint
                         uint64_t out_cap, uint64_t* res, hipStream_t s) {
   if (n == 0) return hipSuccess;
   hipError_t e;
-  const uint32_t nblk = uint32_t((n + kBlock - 1) / kBlock);
   if ((e = ctx->scratch[kScrA].ensure((n + 1) * sizeof(uint64_t))) != hipSuccess) return e;
   if ((e = ctx->scratch[kScrC].ensure(2 * n * sizeof(uint32_t) + 64)) != hipSuccess) return e;
   if ((e = ctx->scratch[kScrSortK].ensure((n + 64) * sizeof(uint32_t))) != hipSuccess) return e;
-  if ((e = ctx->scratch[kScrD].ensure((n + 2) * sizeof(uint64_t))) != hipSuccess) return e;  // hoff
-  if ((e = ctx->scratch[kScrPartial].ensure(uint64_t(nblk) * kProbeFields * sizeof(uint64_t))) != hipSuccess) return e;
   uint64_t* cnt = ctx->scratch[kScrA].as<uint64_t>();
   uint32_t* zo = ctx->scratch[kScrC].as<uint32_t>() + 16;
   uint32_t* po = zo + n;
   uint32_t* nheavy = ctx->scratch[kScrSortK].as<uint32_t>();
-  uint32_t* heavy = nheavy + 64;
-  uint64_t* partials = ctx->scratch[kScrPartial].as<uint64_t>();
   const uint4* mains = t->main.as<const uint4>();
   const bool emit = (flags & HJ3D_PROBE_EMIT) && out;
   if ((e = hipMemsetAsync(nheavy, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
   hipLaunchKernelGGL(k_unnest_slots, dim3(grid_for(ctx, n, kBlock * kItems)), dim3(kBlock), 0, s,
                      static_cast<const uint2*>(in), n, mains, uint32_t(t->n_mains), cnt, zo, po, res);
-  if ((e = exclusive_scan_u64(ctx, cnt, cnt, n, s)) != hipSuccess) return e;
   SlotSrc src{RelView{}, nullptr, mains, zo, po};
   const int ck = (flags & HJ3D_PROBE_CHECKSUM) ? 1 : 2;  // the row sums always
-  if ((e = expand(ctx, src, true, ck, n, cnt, t->sub.as<const uint32_t>(), static_cast<uint2*>(out),
-                  emit ? out_cap : 0, heavy, nheavy, partials, res, s)) != hipSuccess)
-    return e;
-  return reduce_partials(partials, nblk, kProbeFields, 1, res, s);
+  return expand_slots(ctx, src, true, ck, n, cnt, t->sub.as<const uint32_t>(), static_cast<uint2*>(out),
+                      emit ? out_cap : 0, nheavy + 64, nheavy, res, s);
 }
 
 hipError_t nested_build(hj3d_ctx* ctx, hj3d_table* t, const hj3d_rel& r, hipStream_t s) {
@@ -856,57 +883,52 @@ hipError_t nested_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, u
                         uint64_t out_cap, uint64_t* res, hipStream_t s) {
   if (r.n == 0) return hipSuccess;
   const RelView v = view_of(r);
-  const bool unnest = flags & HJ3D_PROBE_UNNEST;
-  const bool emit = (flags & HJ3D_PROBE_EMIT) && out;
+  const int mode = nested_mode(flags, out);
   const uint32_t lo = uint32_t(t->desc.bucket_lo), nbl = t->nb_local;
   const uint32_t* off = t->off.as<const uint32_t>();
   const uint4* mains = t->main.as<const uint4>();
   const uint32_t* sub = t->sub.as<const uint32_t>();
-  uint2* o = static_cast<uint2*>(out);
   const unsigned g = grid_for(ctx, r.n, kBlock * kItems);
   hipError_t e;
-  if (!unnest) {
-    if (emit && (flags & HJ3D_PROBE_MAINREF))
-      hipLaunchKernelGGL(k_nested_probe<kDenseRef>, dim3(g), dim3(kBlock), 0, s, v, t->fm, lo, nbl, off, mains, sub, o,
-                         out_cap, nullptr, nullptr, nullptr, nullptr, res);
-    else if (emit)
-      hipLaunchKernelGGL(k_nested_probe<kDenseNU>, dim3(g), dim3(kBlock), 0, s, v, t->fm, lo, nbl, off, mains, sub, o,
-                         out_cap, nullptr, nullptr, nullptr, nullptr, res);
-    else
-      hipLaunchKernelGGL(k_nested_probe<kAggNU>, dim3(g), dim3(kBlock), 0, s, v, t->fm, lo, nbl, off, mains, sub,
-                         nullptr, 0, nullptr, nullptr, nullptr, nullptr, res);
-    return hipGetLastError();
-  }
-  if (!emit) {
+  // what a mode writes besides the counters: the dense pairs; the heavy groups for k_expand_heavy;
+  // per probe tuple its output count and matched main for the materialised unnest
+  uint2* o = nullptr;
+  uint64_t ocap = 0;
+  uint64_t* cnt = nullptr;
+  uint32_t *nheavy = nullptr, *mid = nullptr;
+  Heavy* hq = nullptr;
+  uint64_t* nhq = nullptr;
+  if (mode == kDenseNU || mode == kDenseRef) {
+    o = static_cast<uint2*>(out);
+    ocap = out_cap;
+  } else if (mode == kAggUN) {
     if ((e = ctx->scratch[kScrC].ensure(r.n * sizeof(Heavy) + 16)) != hipSuccess) return e;
-    uint64_t* nheavy = ctx->scratch[kScrC].as<uint64_t>();
-    Heavy* heavy = reinterpret_cast<Heavy*>(nheavy + 2);
-    if ((e = hipMemsetAsync(nheavy, 0, sizeof(uint64_t), s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_nested_probe<kAggUN>, dim3(g), dim3(kBlock), 0, s, v, t->fm, lo, nbl, off, mains, sub,
-                       nullptr, 0, nullptr, nullptr, heavy, nheavy, res);
-    hipLaunchKernelGGL(k_expand_heavy, dim3(ctx->num_cus * 4), dim3(kBlock), 0, s, heavy, nheavy, mains, sub, res);
-    return hipGetLastError();
+    nhq = ctx->scratch[kScrC].as<uint64_t>();
+    hq = reinterpret_cast<Heavy*>(nhq + 2);
+    if ((e = hipMemsetAsync(nhq, 0, sizeof(uint64_t), s)) != hipSuccess) return e;
+  } else if (mode == kCountUN) {
+    if ((e = ctx->scratch[kScrA].ensure((r.n + 1) * sizeof(uint64_t))) != hipSuccess) return e;
+    if ((e = ctx->scratch[kScrC].ensure(2 * r.n * sizeof(uint32_t) + 64)) != hipSuccess) return e;
+    cnt = ctx->scratch[kScrA].as<uint64_t>();
+    nheavy = ctx->scratch[kScrC].as<uint32_t>();
+    mid = nheavy + 16;
+    if ((e = hipMemsetAsync(nheavy, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
   }
+  // (not through with_mode: the kernels are instantiated, and so emitted, in the order they are named)
+  auto kernel = k_nested_probe<kDenseRef>;
+  if (mode == kDenseNU) kernel = k_nested_probe<kDenseNU>;
+  else if (mode == kAggNU) kernel = k_nested_probe<kAggNU>;
+  else if (mode == kAggUN) kernel = k_nested_probe<kAggUN>;
+  else if (mode == kCountUN) kernel = k_nested_probe<kCountUN>;
+  hipLaunchKernelGGL(kernel, dim3(g), dim3(kBlock), 0, s, v, t->fm, lo, nbl, off, mains, sub, o, ocap, cnt, mid, hq, nhq,
+                     res);
+  if (mode == kAggUN)
+    hipLaunchKernelGGL(k_expand_heavy, dim3(ctx->num_cus * 4), dim3(kBlock), 0, s, hq, nhq, mains, sub, res);
+  if (mode != kCountUN) return hipGetLastError();
   // materialised unnest: count -> scan -> expansion (light: per 256 probes; heavy: all workgroups)
-  const uint32_t nblk = uint32_t((r.n + kBlock - 1) / kBlock);
-  if ((e = ctx->scratch[kScrA].ensure((r.n + 1) * sizeof(uint64_t))) != hipSuccess) return e;
-  if ((e = ctx->scratch[kScrC].ensure(2 * r.n * sizeof(uint32_t) + 64)) != hipSuccess) return e;
-  if ((e = ctx->scratch[kScrD].ensure((r.n + 2) * sizeof(uint64_t))) != hipSuccess) return e;  // hoff
-  if ((e = ctx->scratch[kScrPartial].ensure(uint64_t(nblk) * kProbeFields * sizeof(uint64_t))) != hipSuccess) return e;
-  uint64_t* cnt = ctx->scratch[kScrA].as<uint64_t>();
-  uint32_t* nheavy = ctx->scratch[kScrC].as<uint32_t>();
-  uint32_t* mid = nheavy + 16;
-  uint32_t* heavy = mid + r.n;
-  uint64_t* partials = ctx->scratch[kScrPartial].as<uint64_t>();
-  if ((e = hipMemsetAsync(nheavy, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_nested_probe<kCountUN>, dim3(g), dim3(kBlock), 0, s, v, t->fm, lo, nbl, off, mains, sub,
-                     nullptr, 0, cnt, mid, nullptr, nullptr, res);
-  if ((e = exclusive_scan_u64(ctx, cnt, cnt, r.n, s)) != hipSuccess) return e;
   SlotSrc src{v, mid, mains, nullptr, nullptr};
-  const bool ck = flags & HJ3D_PROBE_CHECKSUM;
-  if ((e = expand(ctx, src, false, ck, r.n, cnt, sub, o, out_cap, heavy, nheavy, partials, res, s)) != hipSuccess)
-    return e;
-  return ck ? reduce_partials(partials, nblk, kProbeFields, 1, res, s) : hipSuccess;
+  return expand_slots(ctx, src, false, (flags & HJ3D_PROBE_CHECKSUM) ? 1 : 0, r.n, cnt, sub, static_cast<uint2*>(out),
+                      out_cap, mid + r.n, nheavy, res, s);
 }
 
 bool radix_nested_applicable(const hj3d_ctx* ctx, const hj3d_table* t, uint64_t n_probe) {
@@ -923,7 +945,7 @@ hipError_t radix_nested_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel
   const double fill = double(t->n_mains) / double(nbl);
   ProbeParts pp;
   unsigned long long* npass = nullptr;  // fused selection: tuples passing it (n_probe)
-  uint32_t w_fit = uint32_t(0.8 * kProbeLdsWords / (1.0 + 4.0 * fill));
+  uint32_t w_fit = uint32_t(kProbeWFrac * kProbeLdsWords / (1.0 + 4.0 * fill));
   if (ctx->pk_slice_max && w_fit > ctx->pk_slice_max) w_fit = ctx->pk_slice_max;  // HJ3D_OPT_PK_SLICE (tests)
   // more LDS slices than the one-level partitioner's 2048 (config D's 1e8-bucket table on one GPU,
   // 2.5e7 / 5e7 buckets per rank at 4 / 2 owners): the packed partitioner's two levels give every
@@ -967,8 +989,6 @@ hipError_t radix_nested_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel
   uint64_t* partials = ctx->scratch[kScrPartial].as<uint64_t>();
   uint64_t* base0 = partials + uint64_t(nblocks + 1) * kProbeFields;
   const uint64_t* base_src = sel ? reinterpret_cast<const uint64_t*>(npass) : res;
-  const bool unnest = flags & HJ3D_PROBE_UNNEST;
-  const bool emit = (flags & HJ3D_PROBE_EMIT) && out;
   const uint32_t* off = t->off.as<const uint32_t>();
   const uint4* mains = t->main.as<const uint4>();
   const uint32_t* sub = t->sub.as<const uint32_t>();
@@ -977,8 +997,7 @@ hipError_t radix_nested_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel
   uint32_t *zo = nullptr, *po = nullptr;
   Heavy* hq = nullptr;
   uint64_t* nhq = nullptr;
-  const int dense = (flags & HJ3D_PROBE_MAINREF) ? kDenseRef : kDenseNU;
-  const int mode = !unnest ? (emit ? dense : kAggNU) : (emit ? kCountUN : kAggUN);
+  const int mode = nested_mode(flags, out);
   if (mode == kCountUN) {
     if ((e = ctx->scratch[kScrA].ensure((r.n + 1) * sizeof(uint64_t))) != hipSuccess) return e;
     if ((e = ctx->scratch[kScrC].ensure(3 * r.n * sizeof(uint32_t) + 64)) != hipSuccess) return e;
@@ -1022,13 +1041,7 @@ hipError_t radix_nested_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel
                          pp.seg + uint64_t(pp.G) * pp.P, off, mains, sub, t->fm, lo, o, out_cap, cnt, zo, po, hq, nhq,
                          res);
     };
-    switch (mode) {
-      case kAggNU: launch(std::integral_constant<int, kAggNU>{}); break;
-      case kDenseNU: launch(std::integral_constant<int, kDenseNU>{}); break;
-      case kDenseRef: launch(std::integral_constant<int, kDenseRef>{}); break;
-      case kAggUN: launch(std::integral_constant<int, kAggUN>{}); break;
-      default: launch(std::integral_constant<int, kCountUN>{}); break;
-    }
+    with_mode(mode, launch);
     if (mode == kAggUN)
       hipLaunchKernelGGL(k_expand_heavy, dim3(ctx->num_cus * 4), dim3(kBlock), 0, s, hq, nhq, mains, sub, res);
   }
@@ -1044,18 +1057,10 @@ hipError_t radix_nested_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel
     return e;
   if (mode != kCountUN) return hipSuccess;
   // expansion over the slots: regions' then overflow pairs' (unused slots have count 0)
-  if ((e = exclusive_scan_u64(ctx, cnt, cnt, r.n, s)) != hipSuccess) return e;
-  const uint32_t nblk = uint32_t((r.n + kBlock - 1) / kBlock);
   // heavy slots: at most one per slot (many probe tuples may match one hot key); nheavy zeroed above
-  if ((e = ctx->scratch[kScrD].ensure((r.n + 2) * sizeof(uint64_t))) != hipSuccess) return e;  // hoff
-  if ((e = ctx->scratch[kScrPartial].ensure(uint64_t(nblk) * kProbeFields * sizeof(uint64_t))) != hipSuccess) return e;
-  uint32_t* heavy = nheavy + 64;
-  partials = ctx->scratch[kScrPartial].as<uint64_t>();
   SlotSrc src{view_of(r), nullptr, mains, zo, po};
-  const bool ck = flags & HJ3D_PROBE_CHECKSUM;
-  if ((e = expand(ctx, src, true, ck, r.n, cnt, sub, o, out_cap, heavy, nheavy, partials, res, s)) != hipSuccess)
-    return e;
-  return ck ? reduce_partials(partials, nblk, kProbeFields, 1, res, s) : hipSuccess;
+  return expand_slots(ctx, src, true, (flags & HJ3D_PROBE_CHECKSUM) ? 1 : 0, r.n, cnt, sub, o, out_cap, nheavy + 64,
+                      nheavy, res, s);
 }
 
 }  // namespace hj3d

@@ -27,7 +27,6 @@ constexpr int kPRounds = 16;
 constexpr int kPTile = kPBlock * kPRounds;       // 16384 tuples per partition tile
 constexpr int kPRoundsR = 8;                     // k_rp_part1r: 8192-tuple tiles
 constexpr int kPSeg = 16;                        // k_rp_part1r: 128-B region segments
-constexpr double kProbeWFrac = 0.8;              // partitioned probes: slice width at this share of the LDS
 // Build kernels load and store through the caches (non-temporal forms measured worse: R is read
 // twice, the pairs re-read by the build and the table by the probe, all from the Infinity Cache).
 __device__ __forceinline__ void put(uint2* p, uint2 e) { *p = e; }
@@ -42,16 +41,12 @@ struct FastDiv {  // exact floor(a / d) for u32 a, 1 <= d < 2^32
   static FastDiv make(uint32_t d) {
     FastDiv f;
     f.m = ~uint64_t(0) / d + 1;
+    f.d1 = d == 1;
     return f;
   }
   __device__ __forceinline__ uint32_t div(uint32_t a) const { return d1 ? a : uint32_t(__umul64hi(m, uint64_t(a))); }
   bool d1 = false;
 };
-inline FastDiv make_div(uint32_t d) {
-  FastDiv f = FastDiv::make(d);
-  f.d1 = d == 1;
-  return f;
-}
 
 // The tuples of one relation, or of two back to back (hj3d_build_many's two tables of one geometry,
 // experiment 4's S and T: one partition pass for both): relation 1's tiles follow relation 0's
@@ -1402,7 +1397,7 @@ Plan plan_for(uint32_t nbl, uint32_t W, uint64_t n) {
   pl.P = uint32_t((uint64_t(nbl) + pl.W - 1) / pl.W);
   if (pl.P == 0) pl.P = 1;
   pl.ntiles = uint32_t((n + kPTile - 1) / kPTile);
-  pl.fw = make_div(pl.W);
+  pl.fw = FastDiv::make(pl.W);
   return pl;
 }
 
@@ -1621,45 +1616,31 @@ hipError_t radix_build(hj3d_ctx* ctx, hj3d_table* t, const hj3d_rel& r, hipStrea
 
 namespace {
 
-struct SegLaunch {
-  const hj3d_table* t;
-  Plan pl;
-  uint32_t G, cap, splits;
-  bool flat;
-  const uint2* region;
-  const uint32_t* counts;
-  const uint32_t* seg;
-  const uint2* ovf;
-  const unsigned long long* novf;
-  int ovf_grid;
-};
-
+// The probe launches over a partitioned probe side: the slices that fit LDS, the wider ones, then the
+// overflow list against the table in HBM.
 template <bool UNIQUE, int MODE, bool CK>
-void launch_seg(const SegLaunch& L, uint2* out, uint64_t cap, uint64_t* cnt, uint64_t* partials, uint64_t* res,
-                hipStream_t s) {
-  const hj3d_table* t = L.t;
-  hipLaunchKernelGGL((k_rp_probe_seg<UNIQUE, MODE, CK, true>), dim3(L.pl.P * L.splits), dim3(kJBlock), 0, s, L.region,
-                     L.counts, L.seg, L.G, L.cap, t->off.as<const uint32_t>(), t->ent.as<const uint2>(), t->fm,
-                     uint32_t(t->desc.bucket_lo), t->nb_local, L.pl.W, L.pl.P, L.splits, L.flat, out, cap, cnt,
-                     partials);
-  hipLaunchKernelGGL((k_rp_probe_seg<UNIQUE, MODE, CK, false>), dim3(L.pl.P * L.splits), dim3(kJBlock), 0, s,
-                     L.region, L.counts, L.seg, L.G, L.cap, t->off.as<const uint32_t>(), t->ent.as<const uint2>(),
-                     t->fm, uint32_t(t->desc.bucket_lo), t->nb_local, L.pl.W, L.pl.P, L.splits, L.flat, out, cap,
-                     cnt, partials);
-  hipLaunchKernelGGL((k_probe_ovf<UNIQUE, MODE, CK>), dim3(L.ovf_grid), dim3(kBlock), 0, s, L.ovf, L.novf,
-                     L.seg + uint64_t(L.G) * L.pl.P, t->off.as<const uint32_t>(), t->ent.as<const uint2>(), t->fm,
+void launch_seg(const hj3d_table* t, const ProbeParts& pp, int ovf_grid, uint2* out, uint64_t cap, uint64_t* cnt,
+                uint64_t* partials, uint64_t* res, hipStream_t s) {
+  hipLaunchKernelGGL((k_rp_probe_seg<UNIQUE, MODE, CK, true>), dim3(pp.P * pp.splits), dim3(kJBlock), 0, s, pp.region,
+                     pp.counts, pp.seg, pp.G, pp.cap, t->off.as<const uint32_t>(), t->ent.as<const uint2>(), t->fm,
+                     uint32_t(t->desc.bucket_lo), t->nb_local, pp.W, pp.P, pp.splits, pp.flat, out, cap, cnt, partials);
+  hipLaunchKernelGGL((k_rp_probe_seg<UNIQUE, MODE, CK, false>), dim3(pp.P * pp.splits), dim3(kJBlock), 0, s, pp.region,
+                     pp.counts, pp.seg, pp.G, pp.cap, t->off.as<const uint32_t>(), t->ent.as<const uint2>(), t->fm,
+                     uint32_t(t->desc.bucket_lo), t->nb_local, pp.W, pp.P, pp.splits, pp.flat, out, cap, cnt, partials);
+  hipLaunchKernelGGL((k_probe_ovf<UNIQUE, MODE, CK>), dim3(ovf_grid), dim3(kBlock), 0, s, pp.ovf, pp.novf,
+                     pp.seg + uint64_t(pp.G) * pp.P, t->off.as<const uint32_t>(), t->ent.as<const uint2>(), t->fm,
                      uint32_t(t->desc.bucket_lo), out, cap, cnt, res);
 }
 
 template <int MODE>
-void launch_seg_any(const SegLaunch& L, bool unique, bool ck, uint2* out, uint64_t cap, uint64_t* cnt,
-                    uint64_t* partials, uint64_t* res, hipStream_t s) {
+void launch_seg_any(const hj3d_table* t, const ProbeParts& pp, int ovf_grid, bool unique, bool ck, uint2* out,
+                    uint64_t cap, uint64_t* cnt, uint64_t* partials, uint64_t* res, hipStream_t s) {
   if (unique) {
-    if (ck) launch_seg<true, MODE, true>(L, out, cap, cnt, partials, res, s);
-    else launch_seg<true, MODE, false>(L, out, cap, cnt, partials, res, s);
+    if (ck) launch_seg<true, MODE, true>(t, pp, ovf_grid, out, cap, cnt, partials, res, s);
+    else launch_seg<true, MODE, false>(t, pp, ovf_grid, out, cap, cnt, partials, res, s);
   } else {
-    if (ck) launch_seg<false, MODE, true>(L, out, cap, cnt, partials, res, s);
-    else launch_seg<false, MODE, false>(L, out, cap, cnt, partials, res, s);
+    if (ck) launch_seg<false, MODE, true>(t, pp, ovf_grid, out, cap, cnt, partials, res, s);
+    else launch_seg<false, MODE, false>(t, pp, ovf_grid, out, cap, cnt, partials, res, s);
   }
 }
 
@@ -1726,9 +1707,7 @@ hipError_t radix_partition_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_
   const uint32_t G = pl.ntiles < uint32_t(ctx->num_cus) ? pl.ntiles : uint32_t(ctx->num_cus);
   // region capacity: expected pairs per (workgroup, partition) + 8 sigma + slack, 128-B multiple
   const uint64_t per_g = uint64_t((pl.ntiles + G - 1) / G) * tile;
-  const double ex = double(per_g < r.n ? per_g : r.n) / P;
-  uint64_t cap = uint64_t(ex + 8.0 * std::sqrt(ex) + 32.0);
-  cap = (cap + 15) & ~uint64_t(15);
+  const uint64_t cap = region_capacity(double(per_g < r.n ? per_g : r.n) / P, 16);
   const uint64_t nreg = uint64_t(G) * P;
   if ((e = ctx->scratch[kScrPairs].ensure(nreg * cap * sizeof(uint2))) != hipSuccess) return e;
   if ((e = ctx->scratch[kScrPHist].ensure((3 * nreg + 2) * sizeof(uint32_t))) != hipSuccess) return e;
@@ -1804,20 +1783,6 @@ hipError_t radix_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, ui
   if ((e = radix_partition_probe(ctx, t, r, uint32_t(kProbeWFrac * kProbeLdsWords / (1.0 + 2.0 * fill)), &pp, s, sel,
                                  sel ? &npass : nullptr)) != hipSuccess)
     return e;
-  SegLaunch L;
-  L.t = t;
-  L.pl.W = pp.W;
-  L.pl.P = pp.P;
-  L.G = pp.G;
-  L.cap = pp.cap;
-  L.splits = pp.splits;
-  L.flat = pp.flat;
-  L.region = pp.region;
-  L.counts = pp.counts;
-  L.seg = pp.seg;
-  L.ovf = pp.ovf;
-  L.novf = pp.novf;
-  L.ovf_grid = ctx->num_cus;
   const uint32_t nblocks = pp.P * pp.splits;
   // one row per probe workgroup + one extra row accumulated with atomics by the non-fitting kernel
   if ((e = ctx->scratch[kScrPartial].ensure(uint64_t(nblocks + 2) * kProbeFields * sizeof(uint64_t))) != hipSuccess)
@@ -1838,17 +1803,17 @@ hipError_t radix_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, ui
   uint2* o = static_cast<uint2*>(out);
   PhaseTimer tk(ctx, HJ3D_T_PROBE_KERNEL);  // for the non-unique EMIT form this includes the offset scan
   if (!emit) {
-    launch_seg_any<kAgg>(L, unique, ck, nullptr, 0, nullptr, partials, res, s);
+    launch_seg_any<kAgg>(t, pp, ctx->num_cus, unique, ck, nullptr, 0, nullptr, partials, res, s);
   } else if (unique) {
-    launch_seg_any<kDense>(L, true, ck, o, out_cap, nullptr, partials, res, s);
+    launch_seg_any<kDense>(t, pp, ctx->num_cus, true, ck, o, out_cap, nullptr, partials, res, s);
   } else {
     if ((e = ctx->scratch[kScrA].ensure((r.n + 1) * sizeof(uint64_t))) != hipSuccess) return e;
     uint64_t* cnt = ctx->scratch[kScrA].as<uint64_t>();
     if ((e = hipMemsetAsync(cnt, 0, (r.n + 1) * sizeof(uint64_t), s)) != hipSuccess) return e;
-    launch_seg_any<kCount>(L, false, ck, nullptr, 0, cnt, partials, res, s);
+    launch_seg_any<kCount>(t, pp, ctx->num_cus, false, ck, nullptr, 0, cnt, partials, res, s);
     // slots of unowned tuples (dropped by the partition) stay 0
     if ((e = exclusive_scan_u64(ctx, cnt, cnt, r.n, s)) != hipSuccess) return e;
-    launch_seg_any<kWrite>(L, false, ck, o, out_cap, cnt, nullptr, res, s);
+    launch_seg_any<kWrite>(t, pp, ctx->num_cus, false, ck, o, out_cap, cnt, nullptr, res, s);
   }
   if ((e = hipGetLastError()) != hipSuccess) return e;
   // n_probe counts every scanned tuple, also those of unowned buckets (dropped by the partition)

@@ -225,6 +225,25 @@ def _torch():
     return torch
 
 
+def _words(t, words: int, what: str, rows: str = "n"):
+    """(ptr, rows) of a contiguous (rows, words) int32 device tensor."""
+    torch = _torch()
+    if not t.is_cuda or t.dtype not in (torch.int32, torch.uint32) or t.dim() != 2 or t.shape[1] != words or \
+            not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous ({rows}, {words}) int32 device tensor")
+    return (t.data_ptr() if t.shape[0] else None), t.shape[0]
+
+
+def _emit_args(out, words=None):
+    """(flag, ptr, cap) for an output tensor: PROBE_EMIT and its buffer, or nothing without one. words=None: a
+    buffer of 8-byte pairs (any shape); else a contiguous (cap, words) int32 device tensor."""
+    if out is None:
+        return 0, None, 0
+    if words is None:
+        return PROBE_EMIT, out.data_ptr(), out.numel() * out.element_size() // 8
+    return (PROBE_EMIT,) + _words(out, words, "out", "cap")
+
+
 class Rel:
     """A device relation: AoS u32 tuples in a torch tensor (no copy)."""
 
@@ -371,11 +390,8 @@ class Context:
         flags = (PROBE_UNIQUE if unique else 0) | (PROBE_UNNEST if unnest else 0) | \
                 (PROBE_CHECKSUM if checksum else 0) | (PROBE_ACCUMULATE if accumulate else 0) | \
                 (PROBE_MAINREF if mainref else 0)
-        ptr, cap = None, 0
-        if out is not None:
-            flags |= PROBE_EMIT
-            ptr, cap = out.data_ptr(), out.numel() * out.element_size() // 8
-        self._check(lib().hj3d_probe(self.h, table.h, C.byref(rel.c), flags, ptr, cap), "hj3d_probe")
+        emit, ptr, cap = _emit_args(out)
+        self._check(lib().hj3d_probe(self.h, table.h, C.byref(rel.c), flags | emit, ptr, cap), "hj3d_probe")
         return self.probe_result() if fetch else None
 
     def probe_result(self) -> ProbeResult:
@@ -392,16 +408,8 @@ class Context:
         out: a contiguous (cap, 3) int32 device tensor that receives the output triples
         (r_row, s_row, t_row), at most cap of them, in no specified order; c_top counts all, and the
         result's `overflow` tells whether some did not fit."""
-        flags = PROBE_CHECKSUM if checksum else 0
-        ptr, cap = None, 0
-        if out is not None:
-            torch = _torch()
-            if not out.is_cuda or out.dtype not in (torch.int32, torch.uint32) or out.dim() != 2 or \
-                    out.shape[1] != 3 or not out.is_contiguous():
-                raise ValueError("out must be a contiguous (cap, 3) int32 device tensor")
-            flags |= PROBE_EMIT
-            cap = out.shape[0]
-            ptr = out.data_ptr() if cap else None
+        emit, ptr, cap = _emit_args(out, 3)
+        flags = (PROBE_CHECKSUM if checksum else 0) | emit
         self._check(lib().hj3d_probe2(self.h, ts.h, tt.h, C.byref(rel.c), flags, ptr, cap), "hj3d_probe2")
         return self.probe2_result() if fetch else None
 
@@ -415,26 +423,15 @@ class Context:
         return d
 
     # ---- deferred unnesting (AlgUnnestHt as an operator of its own) ----
-    @staticmethod
-    def _words(t, words: int, what: str):
-        torch = _torch()
-        if not t.is_cuda or t.dtype not in (torch.int32, torch.uint32) or t.dim() != 2 or t.shape[1] != words or \
-                not t.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous (n, {words}) int32 device tensor")
-        return (t.data_ptr() if t.shape[0] else None), t.shape[0]
-
     def unnest(self, table: "Table", nested, out=None, checksum: bool = True, fetch: bool = True) -> Optional[ProbeResult]:
         """hj3d_unnest: the stored nested tuples `nested` ((n, 2) int32 device tensor of {a, main ref}
         as probe(mainref=True) wrote them, filtered / reordered / concatenated at will; invalid refs
         are skipped) expanded to {a, build row} pairs. out: a contiguous (cap, 2) int32 device tensor
         (None: counters and sums only). n_out counts all pairs; `overflow` tells whether some did not
         fit. checksum=False leaves out the pair hashes (sum_h, xor_h)."""
-        ptr_in, n = self._words(nested, 2, "nested")
-        flags = PROBE_CHECKSUM if checksum else 0
-        ptr, cap = None, 0
-        if out is not None:
-            ptr, cap = self._words(out, 2, "out")
-            flags |= PROBE_EMIT
+        ptr_in, n = _words(nested, 2, "nested")
+        emit, ptr, cap = _emit_args(out, 2)
+        flags = (PROBE_CHECKSUM if checksum else 0) | emit
         self._check(lib().hj3d_unnest(self.h, table.h, ptr_in, n, flags, ptr, cap), "hj3d_unnest")
         return self.probe_result() if fetch else None
 
@@ -443,12 +440,9 @@ class Context:
         """hj3d_unnest2: triples {a, ref_s, ref_t} ((n, 3) int32 device tensor; main refs of ts and tt)
         expanded to every {a, s_row, t_row} of the two groups. out: a contiguous (cap, 3) int32 device
         tensor or None; the result is probe2's dict (c_unnest_1, c_unnest_2, c_top, sums, overflow)."""
-        ptr_in, n = self._words(nested, 3, "nested")
-        flags = PROBE_CHECKSUM if checksum else 0
-        ptr, cap = None, 0
-        if out is not None:
-            ptr, cap = self._words(out, 3, "out")
-            flags |= PROBE_EMIT
+        ptr_in, n = _words(nested, 3, "nested")
+        emit, ptr, cap = _emit_args(out, 3)
+        flags = (PROBE_CHECKSUM if checksum else 0) | emit
         self._check(lib().hj3d_unnest2(self.h, ts.h, tt.h, ptr_in, n, flags, ptr, cap), "hj3d_unnest2")
         return self.probe2_result() if fetch else None
 
@@ -485,12 +479,9 @@ class Context:
             raise ValueError(f"at most {SEL_MAX} predicates")
         flags = (PROBE_UNIQUE if unique else 0) | (PROBE_UNNEST if unnest else 0) | \
                 (PROBE_CHECKSUM if checksum else 0) | (PROBE_MAINREF if mainref else 0)
-        ptr, cap = None, 0
-        if out is not None:
-            flags |= PROBE_EMIT
-            ptr, cap = out.data_ptr(), out.numel() * out.element_size() // 8
-        self._check(lib().hj3d_probe_sel(self.h, table.h, C.byref(rel.c), _sel_preds(preds), len(preds), flags, ptr,
-                                         cap), "hj3d_probe_sel")
+        emit, ptr, cap = _emit_args(out)
+        self._check(lib().hj3d_probe_sel(self.h, table.h, C.byref(rel.c), _sel_preds(preds), len(preds), flags | emit,
+                                         ptr, cap), "hj3d_probe_sel")
         return self.probe_result() if fetch else None
 
     def packed_probe(self, on: bool = True):
