@@ -852,6 +852,59 @@ hj3d_status hj3d_unnest2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* 
   return from_hip(ctx, e, "hj3d_unnest2");
 }
 
+hj3d_status hj3d_probe_ref(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* base, const void* nested_dev, uint64_t n,
+                           uint32_t in_words, uint32_t flags, void* out_dev, uint64_t out_cap) {
+  const char* const me = "hj3d_probe_ref";
+  if (!ctx || !t || !base) return HJ3D_EINVAL;
+  if (const hj3d_status st = unnest_flags_ok(ctx, me, flags); st != HJ3D_OK) return st;
+  if (t->desc.kind != HJ3D_NESTED) return fail_in(ctx, me, "needs a nested table");
+  if (in_words != 1 && in_words != 2) return fail_in(ctx, me, "in_words must be 1 or 2");
+  if (!rel_ok(base) || base->row_off != HJ3D_ROW_IMPLICIT)
+    return fail_in(ctx, me, "invalid base relation (implicit rows only)");
+  if ((n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32)) return fail_in(ctx, me, "invalid input");
+  if (uintptr_t(out_dev) & 3) return fail_in(ctx, me, "misaligned output buffer");
+  if (const hj3d_status st = emit_buffer_ok(ctx, me, flags, out_dev, out_cap); st != HJ3D_OK) return st;
+  if (hipError_t re = resolve(ctx, t); re != hipSuccess) return from_hip(ctx, re, me);
+  uint64_t* res = ctx->res.as<uint64_t>();
+  if (n == 0) {
+    const hipError_t e = hipMemsetAsync(res, 0, kResFields * sizeof(uint64_t), ctx->stream);
+    note_probe(ctx, false, flags, 0, out_cap);
+    return from_hip(ctx, e, me);
+  }
+  // staging relation {key, j, live} behind a 16-byte header (the compaction's cursor), and the dense
+  // output {j, main ref} of the probe over it
+  const uint64_t m = probe_ref_stage_tuples(n);  // n rounded up to whole staging groups
+  hipError_t e = ctx->scratch[kScrRefStage].ensure(16 + m * 3 * sizeof(uint32_t));
+  if (e == hipSuccess) e = ctx->scratch[kScrRefDense].ensure(m * sizeof(uint2));
+  if (e != hipSuccess) return from_hip(ctx, e, me);
+  unsigned long long* cursor = ctx->scratch[kScrRefStage].as<unsigned long long>();
+  uint32_t* stage = ctx->scratch[kScrRefStage].as<uint32_t>() + 4;
+  uint2* dense = ctx->scratch[kScrRefDense].as<uint2>();
+  {
+    PhaseTimer tm(ctx, HJ3D_T_PROBE);
+    e = probe_ref_gather(ctx, nested_dev, n, in_words, *base, stage, dense, cursor, ctx->stream);
+  }
+  if (e != hipSuccess) return from_hip(ctx, e, me);
+  // the live tuples probe t: the selection on the `live` word is fused into the probe partitioner on
+  // the partitioned path, else it runs first (one synchronous count read), as for any hj3d_probe_sel
+  const hj3d_rel staged{stage, m, 12, 0, 4, 0, 0};
+  hj3d_sel_pred live{};
+  live.word_off = 8;
+  live.op = HJ3D_SEL_EQ;
+  live.lo = 1;
+  if (const hj3d_status st = hj3d_probe_sel(ctx, t, &staged, &live, 1, HJ3D_PROBE_MAINREF | HJ3D_PROBE_EMIT, dense, m);
+      st != HJ3D_OK)
+    return st;
+  {
+    PhaseTimer tm(ctx, HJ3D_T_PROBE);
+    e = probe_ref_compact(ctx, t, dense, n, nested_dev, in_words, flags, out_dev, out_cap, cursor, res, ctx->stream);
+    // the non-dense overflow convention: n_out against the capacity, on the stream
+    if (e == hipSuccess) e = out_check(ctx, false, flags, out_cap);
+  }
+  note_probe(ctx, false, flags, n, out_cap);
+  return from_hip(ctx, e, me);
+}
+
 hj3d_status hj3d_probe_geometry(hj3d_ctx* ctx, uint64_t nb_local, uint64_t n_build, uint32_t out[5]) {
   if (!ctx || !out || nb_local == 0 || nb_local >= (1ull << 32)) return HJ3D_EINVAL;
   const PkPlan pl = pk_plan(ctx, uint32_t(nb_local), n_build);

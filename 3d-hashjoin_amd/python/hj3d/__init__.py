@@ -135,6 +135,7 @@ def lib():
         "hj3d_probe2_result": (st, [p, C.POINTER(_Probe2Res)]),
         "hj3d_unnest": (st, [p, p, p, u64, u32, p, u64]),
         "hj3d_unnest2": (st, [p, p, p, p, u64, u32, p, u64]),
+        "hj3d_probe_ref": (st, [p, p, R, p, u64, u32, u32, p, u64]),
         "hj3d_partition": (st, [p, R, u64, u32, p, p]),
         "hj3d_partition_sel": (st, [p, R, C.POINTER(_SelPred), u32, u64, u32, p, p]),
         "hj3d_partition_strided": (st, [p, R, C.POINTER(_SelPred), u32, u64, u32, p, u64, p]),
@@ -445,6 +446,28 @@ class Context:
         flags = (PROBE_CHECKSUM if checksum else 0) | emit
         self._check(lib().hj3d_unnest2(self.h, ts.h, tt.h, ptr_in, n, flags, ptr, cap), "hj3d_unnest2")
         return self.probe2_result() if fetch else None
+
+    # ---- the chained nested probe (AlgNestJoinProbe over another nested probe's output) ----
+    def probe_ref(self, table: "Table", base: Rel, nested, out=None, checksum: bool = True,
+                  fetch: bool = True) -> Optional[ProbeResult]:
+        """hj3d_probe_ref: the stored nested tuples `nested` (a contiguous (n, 1) or (n, 2) int32
+        device tensor of {a} / {a, main ref}; a = a row of `base`, the probe-side relation with
+        implicit rows) probe `table` with the key word of base row a. Dead tuples (a outside base, or
+        a ref of 0xFFFFFFFF) are skipped and not counted. out: a contiguous (cap, words + 1) int32
+        device tensor that receives every matching tuple with the main ref of `table` appended
+        (None: counters and sums only). n_probe = live tuples, n_matched = n_out = those with a
+        match; `overflow` tells whether some did not fit."""
+        torch = _torch()
+        if not nested.is_cuda or nested.dtype not in (torch.int32, torch.uint32) or nested.dim() != 2 or \
+                nested.shape[1] not in (1, 2) or not nested.is_contiguous():
+            raise ValueError("nested must be a contiguous (n, 1) or (n, 2) int32 device tensor")
+        words = nested.shape[1]
+        ptr_in, n = _words(nested, words, "nested")
+        emit, ptr, cap = _emit_args(out, words + 1)
+        flags = (PROBE_CHECKSUM if checksum else 0) | emit
+        self._check(lib().hj3d_probe_ref(self.h, table.h, C.byref(base.c), ptr_in, n, words, flags, ptr, cap),
+                    "hj3d_probe_ref")
+        return self.probe_result() if fetch else None
 
     # ---- selection pushdown (AlgSelection / AlgDynSelection, algebra.hh:278-358) ----
     def select(self, rel: Rel, preds, out_pairs=None, count=None, fetch: bool = True):
@@ -870,5 +893,5 @@ class Table:
 
 
 from .plans import (EXP1_PLANS, exp1_plan, exp1_plan_sharded, exp1_relations_ref, exp4_plan,  # noqa: E402,F401
-                    exp4_plan_sharded, exp4_relations_ref, merge_exp4, merge_shard_stats, num_buckets_exp1,
+                    exp4_plan_chained, exp4_plan_sharded, exp4_relations_ref, merge_exp4, merge_shard_stats, num_buckets_exp1,
                     num_distinct_sharded)

@@ -244,6 +244,29 @@ def exp4_plan(ctx: Context, plan: str, R, S, T, nb: int, fused: bool = True, out
     return r
 
 
+def exp4_plan_chained(ctx: Context, R, S, T, nb, keys=(0, 0), out=None, checksum: bool = True) -> dict:
+    """Experiment-4 Ndu from the separate operators (main_experiment4.cc:847-850 as written: the second
+    nested probe takes the first one's output): two nested tables on S.a and T.a, then
+    probe(ts, mainref) -> probe_ref(tt, base=R) -> unnest2, all on the device. keys: the R words of
+    the two join attributes (R.keys[0] = S.a, R.keys[1] = T.a), which hj3d_probe2 needs equal; nb: the
+    bucket count of both tables, or a pair (S table, T table). Returns Context.probe2_result()'s keys:
+    c_probe_rs* from the first probe, c_probe_rt* from probe_ref (its input is only the first probe's
+    survivors, as in the reference), the rest from unnest2. out: a (cap, 3) int32 device tensor for
+    the output triples."""
+    import torch
+    nb_s, nb_t = (nb, nb) if isinstance(nb, int) else nb
+    ts, tt = Table(ctx, HJ3D_NESTED, nb_s), Table(ctx, HJ3D_NESTED, nb_t)
+    ctx.build_many([ts, tt], [Rel(S, key_word=1), Rel(T, key_word=1)])
+    n = R.shape[0]
+    pairs = torch.empty((max(n, 1), 2), dtype=torch.int32, device=R.device)
+    rs = ctx.probe(ts, Rel(R, key_word=keys[0]), out=pairs, mainref=True, checksum=False)
+    trip = torch.empty((max(rs.n_matched, 1), 3), dtype=torch.int32, device=R.device)
+    rt = ctx.probe_ref(tt, Rel(R, key_word=keys[1]), pairs[:n], out=trip, checksum=False)
+    res = ctx.unnest2(ts, tt, trip[:rt.n_out], out=out, checksum=checksum)
+    res.update(c_probe_rs=rs.n_matched, c_probe_rs_cmp=rs.n_cmps, c_probe_rt=rt.n_matched, c_probe_rt_cmp=rt.n_cmps)
+    return res
+
+
 EXP4_SUM = ("c_probe_rs", "c_probe_rs_cmp", "c_probe_rt", "c_probe_rt_cmp", "c_unnest_1", "c_unnest_2", "c_top",
             "sum_a", "sum_b", "sum_c", "sum_h")
 

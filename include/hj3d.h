@@ -18,7 +18,10 @@
  *   hj3d_unnest                AlgUnnestHt::step as a separate operator over stored nested tuples
  *                              {a, main ref} (HJ3D_PROBE_MAINREF)     algebra.hh:490-541
  *   hj3d_unnest2               the two stacked unnests of experiment 4  main_experiment4.cc:435-466
- *   hj3d_table_stats           HtChaining1/HtNested1::makeStatistics  ht_chaining.hh:260-292,
+ *   hj3d_probe_ref             AlgNestJoinProbe::step driven by another AlgNestJoinProbe: the probe
+ *                              input is stored nested tuples           algebra.hh:435-459,
+ *                                                                     main_experiment4.cc:847-850
+ *   hj3d_table_stats          HtChaining1/HtNested1::makeStatistics  ht_chaining.hh:260-292,
  *                                                                     ht_nested.hh:450-482
  *   hj3d_table_clear           HtChaining1/HtNested1::clear           ht_chaining.hh:250-258,
  *                                                                     ht_nested.hh:438-447
@@ -390,6 +393,39 @@ hj3d_status hj3d_unnest(hj3d_ctx* ctx, const hj3d_table* t, const void* nested_d
  * counters) if c_top > out_cap. */
 hj3d_status hj3d_unnest2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const void* nested_dev,
                          uint64_t n, uint32_t flags, void* out_dev, uint64_t out_cap);
+/* hj3d_probe_ref: the chained nested probe. Replaces AlgNestJoinProbe::step (algebra.hh:435-459) driven
+ * by another AlgNestJoinProbe, i.e. the second probe of experiment 4's strand, whose input is the first
+ * probe's nested output (probe_RS_t over probe_RT_t, main_experiment4.cc:847-850), without
+ * hj3d_probe2's restriction to one probe attribute: probe -> probe_ref -> ... -> unnest runs an n-way
+ * nested join on different attributes on the device.
+ * nested_dev: n stored nested tuples of in_words u32 words each (4-byte aligned): {a} (in_words 1) or
+ * {a, ref} (in_words 2: what a HJ3D_PROBE_MAINREF probe wrote, its dense output as it stands,
+ * 0xFFFFFFFF refs included, or filtered, reordered or concatenated since). a is a row id of `base`, the
+ * probe-side relation (implicit rows: tuple index a - base->row_base); the join key is the u32 at
+ * base->key_off of that tuple. A tuple is live iff a is a row of base and (in_words 2) its ref is not
+ * 0xFFFFFFFF. A dead tuple is skipped, as AlgNestJoinProbe passes nothing downstream without a match:
+ * not probed, not counted, and no memory is read through it. Carried refs are opaque: copied, never
+ * dereferenced. Every live tuple probes `t` (HJ3D_NESTED) with its key, each occurrence of a row on
+ * its own (a tuple is identified by its position in the input, not by a).
+ * With HJ3D_PROBE_EMIT every live tuple that finds its key yields one tuple of in_words + 1 words, the
+ * input tuple followed by the main_ref of t (as HJ3D_PROBE_MAINREF): compact, in no specified order,
+ * at most out_cap of them; nothing is written at or beyond out_dev + 4 * (in_words + 1) * out_cap. The
+ * output feeds hj3d_unnest (in_words 1), hj3d_unnest2 (in_words 2) or another hj3d_probe_ref.
+ * Result (hj3d_probe_result): n_probe = live tuples, n_matched = n_out = live tuples with a match,
+ * n_cmps = the collision-chain comparisons of exactly those probes (bit-exact: what hj3d_probe reports
+ * for a relation of the live tuples' keys), sum_a = the sum of a over the output tuples (always); with
+ * HJ3D_PROBE_CHECKSUM sum_b = the sum of the matched main records' first build rows and sum_h / xor_h
+ * fold pair(a, first build row) (else 0); sum_c = 0. HJ3D_EOVERFLOW (complete counters) if
+ * n_out > out_cap. A cleared table gives n_probe = live tuples and every other counter 0.
+ * flags: HJ3D_PROBE_EMIT and HJ3D_PROBE_CHECKSUM only. HJ3D_EINVAL: any other flag, a null ctx / t /
+ * base, a chaining table, in_words not 1 or 2, EMIT with out_dev == NULL and out_cap > 0, nested_dev or
+ * out_dev not 4-byte aligned, n && !nested_dev, n >= 2^32, an invalid base or one with explicit rows.
+ * nested_dev and out_dev must not overlap. A nested build still pending is finished first, as by a
+ * probe. Runs as hj3d_probe_sel over a staged relation of the tuples' keys (all probe paths apply):
+ * asynchronous on the partitioned probe path, where the liveness test is fused into the probe
+ * partitioner; otherwise the call waits for the stream once (the live count is read). */
+hj3d_status hj3d_probe_ref(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* base, const void* nested_dev,
+                           uint64_t n, uint32_t in_words, uint32_t flags, void* out_dev, uint64_t out_cap);
 
 /* ---- multi-GPU exchange helpers (bucket-range radix partition) ----
  * Destination of a tuple: owner(bucket) = bucket * nparts / num_buckets. Writes (key,row)
