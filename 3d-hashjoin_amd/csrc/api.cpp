@@ -143,14 +143,17 @@ hj3d_status table_gbar_check(hj3d_ctx* ctx, const hj3d_table* t) {
   return fail(ctx, HJ3D_EDEVICE, "fused build partition: a grid barrier timed out, the table is invalid (rebuild it)");
 }
 
-// The result slot on the host, for both result getters: copied behind the strand, with the barrier word.
-hj3d_status read_result(hj3d_ctx* ctx, const char* what, uint64_t h[kResFields]) {
+// A result slot on the host, for the result getters: copied behind the strand, with the barrier word.
+hj3d_status read_slot(hj3d_ctx* ctx, const char* what, const void* slot, uint64_t* h, int words) {
   uint64_t gw = 0;
-  hipError_t e = hipMemcpyAsync(h, ctx->res.p, kResFields * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e = hipMemcpyAsync(h, slot, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = gbar_copy(ctx, &gw);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) return from_hip(ctx, e, what);
   return gbar_check(ctx, gw);
+}
+hj3d_status read_result(hj3d_ctx* ctx, const char* what, uint64_t h[kResFields]) {
+  return read_slot(ctx, what, ctx->res.p, h, kResFields);
 }
 
 // The partitioned probe sizes its LDS slices by the number of main records: a nested build's counts
@@ -351,6 +354,7 @@ void hj3d_ctx_destroy(hj3d_ctx* ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   for (auto& b : ctx->scratch) b.release();
   ctx->res.release();
+  ctx->resn.release();
   ctx->misc.release();
   ctx->ctl.release();
   ctx->scan_status.release();
@@ -852,13 +856,17 @@ hj3d_status hj3d_unnest2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* 
   return from_hip(ctx, e, "hj3d_unnest2");
 }
 
-hj3d_status hj3d_probe_ref(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* base, const void* nested_dev, uint64_t n,
-                           uint32_t in_words, uint32_t flags, void* out_dev, uint64_t out_cap) {
-  const char* const me = "hj3d_probe_ref";
+// hj3d_probe_ref (max_words 2: the {a} / {a, ref} kernels of probe_ref.hip) and hj3d_probe_refn
+// (max_words HJ3D_NEST_MAX: probe_refn.hip's, one instantiation per width)
+static hj3d_status probe_ref_any(hj3d_ctx* ctx, const char* me, uint32_t max_words, const hj3d_table* t,
+                                 const hj3d_rel* base, const void* nested_dev, uint64_t n, uint32_t in_words,
+                                 uint32_t flags, void* out_dev, uint64_t out_cap) {
   if (!ctx || !t || !base) return HJ3D_EINVAL;
+  const bool wide = max_words > 2;
   if (const hj3d_status st = unnest_flags_ok(ctx, me, flags); st != HJ3D_OK) return st;
   if (t->desc.kind != HJ3D_NESTED) return fail_in(ctx, me, "needs a nested table");
-  if (in_words != 1 && in_words != 2) return fail_in(ctx, me, "in_words must be 1 or 2");
+  if (in_words < 1 || in_words > max_words)
+    return fail_in(ctx, me, wide ? "in_words must be 1 .. HJ3D_NEST_MAX" : "in_words must be 1 or 2");
   if (!rel_ok(base) || base->row_off != HJ3D_ROW_IMPLICIT)
     return fail_in(ctx, me, "invalid base relation (implicit rows only)");
   if ((n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32)) return fail_in(ctx, me, "invalid input");
@@ -882,7 +890,8 @@ hj3d_status hj3d_probe_ref(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* b
   uint2* dense = ctx->scratch[kScrRefDense].as<uint2>();
   {
     PhaseTimer tm(ctx, HJ3D_T_PROBE);
-    e = probe_ref_gather(ctx, nested_dev, n, in_words, *base, stage, dense, cursor, ctx->stream);
+    e = (wide ? probe_refn_gather : probe_ref_gather)(ctx, nested_dev, n, in_words, *base, stage, dense, cursor,
+                                                      ctx->stream);
   }
   if (e != hipSuccess) return from_hip(ctx, e, me);
   // the live tuples probe t: the selection on the `live` word is fused into the probe partitioner on
@@ -897,12 +906,75 @@ hj3d_status hj3d_probe_ref(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* b
     return st;
   {
     PhaseTimer tm(ctx, HJ3D_T_PROBE);
-    e = probe_ref_compact(ctx, t, dense, n, nested_dev, in_words, flags, out_dev, out_cap, cursor, res, ctx->stream);
+    e = (wide ? probe_refn_compact : probe_ref_compact)(ctx, t, dense, n, nested_dev, in_words, flags, out_dev,
+                                                        out_cap, cursor, res, ctx->stream);
     // the non-dense overflow convention: n_out against the capacity, on the stream
     if (e == hipSuccess) e = out_check(ctx, false, flags, out_cap);
   }
   note_probe(ctx, false, flags, n, out_cap);
   return from_hip(ctx, e, me);
+}
+
+hj3d_status hj3d_probe_ref(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* base, const void* nested_dev, uint64_t n,
+                           uint32_t in_words, uint32_t flags, void* out_dev, uint64_t out_cap) {
+  return probe_ref_any(ctx, "hj3d_probe_ref", 2, t, base, nested_dev, n, in_words, flags, out_dev, out_cap);
+}
+
+hj3d_status hj3d_probe_refn(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* base, const void* nested_dev,
+                            uint64_t n, uint32_t in_words, uint32_t flags, void* out_dev, uint64_t out_cap) {
+  return probe_ref_any(ctx, "hj3d_probe_refn", HJ3D_NEST_MAX, t, base, nested_dev, n, in_words, flags, out_dev,
+                       out_cap);
+}
+
+hj3d_status hj3d_unnestn(hj3d_ctx* ctx, const hj3d_table* const* tables, uint32_t k, const void* nested_dev,
+                         uint64_t n, uint32_t flags, void* out_dev, uint64_t out_cap) {
+  const char* const me = "hj3d_unnestn";
+  if (!ctx || !tables) return HJ3D_EINVAL;
+  if (k < 1 || k > HJ3D_NEST_MAX) return fail_in(ctx, me, "k must be 1 .. HJ3D_NEST_MAX");
+  for (uint32_t i = 0; i < k; ++i)
+    if (!tables[i]) return fail_in(ctx, me, "a null table");
+  if (const hj3d_status st = unnest_flags_ok(ctx, me, flags); st != HJ3D_OK) return st;
+  for (uint32_t i = 0; i < k; ++i)
+    if (tables[i]->desc.kind != HJ3D_NESTED) return fail_in(ctx, me, "needs nested tables");
+  if ((n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32)) return fail_in(ctx, me, "invalid input");
+  if (uintptr_t(out_dev) & 3) return fail_in(ctx, me, "misaligned output buffer");
+  if (const hj3d_status st = emit_buffer_ok(ctx, me, flags, out_dev, out_cap); st != HJ3D_OK) return st;
+  for (uint32_t i = 0; i < k; ++i)
+    if (hipError_t re = resolve(ctx, tables[i]); re != hipSuccess) return from_hip(ctx, re, me);
+  if (hipError_t ae = ctx->resn.ensure(kUnnWords * sizeof(uint64_t)); ae != hipSuccess) return from_hip(ctx, ae, me);
+  PhaseTimer tm(ctx, HJ3D_T_PROBE);
+  const hipError_t e =
+      unnest_wide(ctx, tables, k, nested_dev, n, flags, out_dev, out_cap, ctx->resn.as<uint64_t>(), ctx->stream);
+  ctx->resn_n = n;
+  ctx->resn_flags = flags;
+  ctx->resn_cap = (flags & HJ3D_PROBE_EMIT) ? out_cap : ~0ull;
+  return from_hip(ctx, e, me);
+}
+
+hj3d_status hj3d_unnestn_result(hj3d_ctx* ctx, hj3d_unnestn_res* out) {
+  if (!ctx || !out) return HJ3D_EINVAL;
+  std::memset(out, 0, sizeof(*out));
+  if (!ctx->resn.p) return fail(ctx, HJ3D_EINVAL, "hj3d_unnestn_result: no hj3d_unnestn before it");
+  uint64_t h[kUnnWords];
+  if (const hj3d_status st = read_slot(ctx, "hj3d_unnestn_result", ctx->resn.p, h, kUnnWords); st != HJ3D_OK) return st;
+  out->n_in = ctx->resn_n;
+  out->n_live = h[0];
+  // the magnitude rule: a product, or the total (from the sums of the products' halves: no carry is
+  // lost), at or beyond 2^63; the expansion did not run
+  if (h[kUnnFlag] != 0 || h[kUnnHi] + (h[kUnnLo] >> 32) >= (1ull << 31))
+    return fail(ctx, HJ3D_EUNSUPPORTED, "hj3d_unnestn: a tuple's product or c_top reaches 2^63");
+  for (int j = 0; j < HJ3D_NEST_MAX; ++j) {
+    out->c_unnest[j] = h[1 + j];
+    out->sum_row[j] = h[kUnnSumA + 1 + j];
+  }
+  out->c_top = h[kUnnCTop];
+  out->sum_a = h[kUnnSumA];
+  out->sum_h = h[kUnnSumA + 1 + HJ3D_NEST_MAX];
+  out->xor_h = h[kUnnSumA + 2 + HJ3D_NEST_MAX];
+  // c_top counts every row; those past the buffer were dropped
+  if ((ctx->resn_flags & HJ3D_PROBE_EMIT) && out->c_top > ctx->resn_cap)
+    return fail(ctx, HJ3D_EOVERFLOW, "hj3d_unnestn: output buffer too small");
+  return HJ3D_OK;
 }
 
 hj3d_status hj3d_probe_geometry(hj3d_ctx* ctx, uint64_t nb_local, uint64_t n_build, uint32_t out[5]) {

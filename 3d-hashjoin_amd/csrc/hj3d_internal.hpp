@@ -30,6 +30,12 @@ namespace hj3d {
 
 constexpr int kBlock = 256;           // 4 waves; the default workgroup of every streaming kernel
 constexpr uint32_t kInvalid = 0xFFFFFFFFu;
+constexpr uint32_t kRefGroup = 8;     // hj3d_probe_ref / hj3d_probe_refn: tuples per staging group (probe_ref.hip)
+// hj3d_unnestn's device result slot (u64 words): n_live, c_unnest[HJ3D_NEST_MAX], c_top, then the
+// magnitude words (the sum of the products' high and of their low halves, the tuples whose product
+// reached 2^63), then sum_a, sum_row[HJ3D_NEST_MAX], sum_h, xor_h (unnestn.hip)
+constexpr int kUnnCTop = 1 + HJ3D_NEST_MAX, kUnnHi = kUnnCTop + 1, kUnnLo = kUnnHi + 1, kUnnFlag = kUnnLo + 1;
+constexpr int kUnnSumA = kUnnFlag + 1, kUnnWords = kUnnSumA + 3 + HJ3D_NEST_MAX;
 
 // Grow-only device buffer (allocation happens outside timed loops once sizes are warm).
 struct DevBuf {
@@ -141,6 +147,11 @@ struct hj3d_ctx {
   uint64_t gbar_seq = 0;
   uint64_t diag_lb = 0;    // HJ3D_OPT_DIAG_LOOKBACK: slice-path look-back wait limit in 100 MHz ticks, partition 0 silent
   uint64_t diag_gbar = 0;  // HJ3D_OPT_DIAG_GBAR: barrier timeout in 100 MHz ticks, workgroup 0 never arrives
+  // hj3d_unnestn: its own result slot (kUnnWords words), the input tuples, flags and output
+  // capacity of the last call (hj3d_unnestn_result)
+  hj3d::DevBuf resn;
+  uint64_t resn_n = 0, resn_cap = ~0ull;
+  uint32_t resn_flags = 0;
   hipError_t ensure_ctl() {
     if (ctl.p) return hipSuccess;
     hipError_t e = ctl.ensure(128 * sizeof(uint64_t));  // 8 control words; [64, 128): store sink
@@ -448,6 +459,19 @@ hipError_t probe_ref_gather(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t 
 hipError_t probe_ref_compact(hj3d_ctx* ctx, const hj3d_table* t, const uint2* dense, uint64_t n, const void* in,
                              uint32_t words, uint32_t flags, void* out, uint64_t out_cap, unsigned long long* cursor,
                              uint64_t* res_dev, hipStream_t s);
+// probe_refn.hip: the same two kernels for tuples of 1..HJ3D_NEST_MAX words {a, ref_1 ..} (hj3d_probe_refn);
+// staging order, dense slots and cursor as above (probe_ref_mult: the staging permutation's multiplier
+// for ng groups)
+uint64_t probe_ref_mult(uint64_t ng);
+hipError_t probe_refn_gather(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t words, const hj3d_rel& base,
+                             uint32_t* stage, uint2* dense, unsigned long long* cursor, hipStream_t s);
+hipError_t probe_refn_compact(hj3d_ctx* ctx, const hj3d_table* t, const uint2* dense, uint64_t n, const void* in,
+                              uint32_t words, uint32_t flags, void* out, uint64_t out_cap, unsigned long long* cursor,
+                              uint64_t* res_dev, hipStream_t s);
+// unnestn.hip: hj3d_unnestn, n tuples {a, ref_1 .. ref_k} of tables[0 .. k) expanded to {a, row_1 .. row_k}
+// (res: the kUnnWords words of ctx->resn, cleared here)
+hipError_t unnest_wide(hj3d_ctx* ctx, const hj3d_table* const* tables, uint32_t k, const void* in, uint64_t n,
+                       uint32_t flags, void* out, uint64_t out_cap, uint64_t* res_dev, hipStream_t s);
 // exp4.hip
 hipError_t probe2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const hj3d_rel& r, uint32_t flags,
                   void* out, uint64_t out_cap, uint64_t* res_dev, hipStream_t s);

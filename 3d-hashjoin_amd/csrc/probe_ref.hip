@@ -32,7 +32,7 @@ constexpr uint32_t kTile = kBlock * kItems;  // slots per workgroup and cursor c
 // tuples (one 64-B read at 8 B per tuple) permuted by a multiplier coprime to the ng groups, near
 // ng / golden ratio, so any run of staging tuples samples the whole input evenly. The last group's
 // positions past n become dead staging tuples.
-constexpr uint32_t kGroup = 8;
+constexpr uint32_t kGroup = kRefGroup;
 
 __global__ __launch_bounds__(kBlock) void k_pref_gather(const uint32_t* __restrict__ in, uint64_t n, uint32_t words,
                                                         RelView base, uint64_t ng, uint64_t mult,
@@ -132,9 +132,7 @@ __global__ __launch_bounds__(kBlock) void k_pref_compact(const uint2* __restrict
 
 uint64_t probe_ref_stage_tuples(uint64_t n) { return (n + kGroup - 1) / kGroup * kGroup; }
 
-hipError_t probe_ref_gather(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t words, const hj3d_rel& base,
-                            uint32_t* stage, uint2* dense, unsigned long long* cursor, hipStream_t s) {
-  const uint64_t ng = probe_ref_stage_tuples(n) / kGroup;
+uint64_t probe_ref_mult(uint64_t ng) {
   // the odd multiplier nearest ng / golden ratio that is coprime to ng (a bijection on the groups)
   uint64_t mult = uint64_t(double(ng) * 0.6180339887498949) | 1;
   auto gcd = [](uint64_t a, uint64_t b) {
@@ -146,6 +144,13 @@ hipError_t probe_ref_gather(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t 
     return a;
   };
   while (gcd(mult, ng) != 1) mult += 2;
+  return mult;
+}
+
+hipError_t probe_ref_gather(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t words, const hj3d_rel& base,
+                            uint32_t* stage, uint2* dense, unsigned long long* cursor, hipStream_t s) {
+  const uint64_t ng = probe_ref_stage_tuples(n) / kGroup;
+  const uint64_t mult = probe_ref_mult(ng);
   hipLaunchKernelGGL(k_pref_gather, dim3(grid_for(ctx, ng * kGroup, kBlock * 4)), dim3(kBlock), 0, s,
                      static_cast<const uint32_t*>(in), n, words, view_of(base), ng, mult, stage, dense, cursor);
   return hipGetLastError();

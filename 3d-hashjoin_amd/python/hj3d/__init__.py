@@ -25,6 +25,7 @@ HJ3D_ROW_IMPLICIT = 0xFFFFFFFF
 HJ3D_CHAIN, HJ3D_NESTED = 0, 1
 PROBE_UNIQUE, PROBE_UNNEST, PROBE_EMIT, PROBE_CHECKSUM, PROBE_ACCUMULATE = 0x1, 0x2, 0x4, 0x8, 0x10
 PROBE_MAINREF = 0x20
+HJ3D_NEST_MAX = 6  # main refs a stored nested tuple may carry (probe_refn, unnestn)
 T_BUILD, T_PROBE, T_PROBE_KERNEL, T_PARTITION, T_SCATTER, T_HIST = range(6)
 OPT_FORCE_DIRECT, OPT_RADIX_MIN, OPT_NESTED_SORT, OPT_SEL_UNFUSED, OPT_PACKED_PROBE = 1, 2, 4, 5, 6
 OPT_PROBE_ITEMS = 7
@@ -64,6 +65,12 @@ class _Probe2Res(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("c_probe_rs", "c_probe_rs_cmp", "c_probe_rt", "c_probe_rt_cmp",
                                           "c_unnest_1", "c_unnest_2", "c_top", "sum_a", "sum_b", "sum_c", "sum_h",
                                           "xor_h")]
+
+
+class _UnnestNRes(C.Structure):
+    _fields_ = [("n_in", C.c_uint64), ("n_live", C.c_uint64), ("c_unnest", C.c_uint64 * HJ3D_NEST_MAX),
+                ("c_top", C.c_uint64), ("sum_a", C.c_uint64), ("sum_row", C.c_uint64 * HJ3D_NEST_MAX),
+                ("sum_h", C.c_uint64), ("xor_h", C.c_uint64)]
 
 
 class _SelPred(C.Structure):
@@ -136,6 +143,9 @@ def lib():
         "hj3d_unnest": (st, [p, p, p, u64, u32, p, u64]),
         "hj3d_unnest2": (st, [p, p, p, p, u64, u32, p, u64]),
         "hj3d_probe_ref": (st, [p, p, R, p, u64, u32, u32, p, u64]),
+        "hj3d_probe_refn": (st, [p, p, R, p, u64, u32, u32, p, u64]),
+        "hj3d_unnestn": (st, [p, C.POINTER(p), u32, p, u64, u32, p, u64]),
+        "hj3d_unnestn_result": (st, [p, C.POINTER(_UnnestNRes)]),
         "hj3d_partition": (st, [p, R, u64, u32, p, p]),
         "hj3d_partition_sel": (st, [p, R, C.POINTER(_SelPred), u32, u64, u32, p, p]),
         "hj3d_partition_strided": (st, [p, R, C.POINTER(_SelPred), u32, u64, u32, p, u64, p]),
@@ -468,6 +478,58 @@ class Context:
         self._check(lib().hj3d_probe_ref(self.h, table.h, C.byref(base.c), ptr_in, n, words, flags, ptr, cap),
                     "hj3d_probe_ref")
         return self.probe_result() if fetch else None
+
+    # ---- wide nested tuples: the chain and the unnest over up to HJ3D_NEST_MAX tables ----
+    def probe_refn(self, table: "Table", base: Rel, nested, out=None, checksum: bool = True,
+                   fetch: bool = True) -> Optional[ProbeResult]:
+        """hj3d_probe_refn: probe_ref for a contiguous (n, 1..HJ3D_NEST_MAX) int32 device tensor of
+        {a, ref_1 ..}: a tuple is live iff a is a row of `base` and none of its carried refs is
+        0xFFFFFFFF. out: a contiguous (cap, words + 1) int32 device tensor that receives every
+        matching tuple with the main ref of `table` appended, so the output feeds probe_refn again
+        or unnestn. The result is probe_ref's."""
+        torch = _torch()
+        if not nested.is_cuda or nested.dtype not in (torch.int32, torch.uint32) or nested.dim() != 2 or \
+                not 1 <= nested.shape[1] <= HJ3D_NEST_MAX or not nested.is_contiguous():
+            raise ValueError(f"nested must be a contiguous (n, 1..{HJ3D_NEST_MAX}) int32 device tensor")
+        words = nested.shape[1]
+        ptr_in, n = _words(nested, words, "nested")
+        emit, ptr, cap = _emit_args(out, words + 1)
+        flags = (PROBE_CHECKSUM if checksum else 0) | emit
+        self._check(lib().hj3d_probe_refn(self.h, table.h, C.byref(base.c), ptr_in, n, words, flags, ptr, cap),
+                    "hj3d_probe_refn")
+        return self.probe_result() if fetch else None
+
+    def unnestn(self, tables, nested, out=None, checksum: bool = True, fetch: bool = True) -> Optional[dict]:
+        """hj3d_unnestn: tuples {a, ref_1 .. ref_k} (a contiguous (n, k + 1) int32 device tensor; ref_i a
+        main ref of tables[i - 1], k = len(tables) <= HJ3D_NEST_MAX, a table may repeat) expanded to
+        every {a, row_1 .. row_k} of the k groups. out: a contiguous (cap, k + 1) int32 device tensor
+        or None (counters and sums only). The result is unnestn_result()'s dict."""
+        k = len(tables)
+        if not 1 <= k <= HJ3D_NEST_MAX:
+            raise ValueError(f"unnestn takes 1..{HJ3D_NEST_MAX} tables")
+        ptr_in, n = _words(nested, k + 1, "nested")
+        emit, ptr, cap = _emit_args(out, k + 1)
+        flags = (PROBE_CHECKSUM if checksum else 0) | emit
+        th = (C.c_void_p * k)(*[t.h for t in tables])
+        self._check(lib().hj3d_unnestn(self.h, th, k, ptr_in, n, flags, ptr, cap), "hj3d_unnestn")
+        self._unnestn_k = k
+        return self.unnestn_result() if fetch else None
+
+    def unnestn_result(self) -> dict:
+        """The last unnestn's result: n_in, n_live, c_unnest (list of k: the outputs of the unnests in
+        the order the reference executes them, the last table first), c_top, sum_a, sum_row (list of
+        k), sum_h, xor_h, overflow. Raises Hj3dError(HJ3D_EUNSUPPORTED) when a tuple's product or
+        c_top reaches 2^63."""
+        r = _UnnestNRes()
+        st = lib().hj3d_unnestn_result(self.h, C.byref(r))
+        if st not in (HJ3D_OK, HJ3D_EOVERFLOW):
+            self._check(st, "hj3d_unnestn_result")
+        k = getattr(self, "_unnestn_k", HJ3D_NEST_MAX)
+        d = {f: getattr(r, f) for f in ("n_in", "n_live", "c_top", "sum_a", "sum_h", "xor_h")}
+        d["c_unnest"] = list(r.c_unnest)[:k]
+        d["sum_row"] = list(r.sum_row)[:k]
+        d["overflow"] = st == HJ3D_EOVERFLOW
+        return d
 
     # ---- selection pushdown (AlgSelection / AlgDynSelection, algebra.hh:278-358) ----
     def select(self, rel: Rel, preds, out_pairs=None, count=None, fetch: bool = True):
@@ -894,4 +956,4 @@ class Table:
 
 from .plans import (EXP1_PLANS, exp1_plan, exp1_plan_sharded, exp1_relations_ref, exp4_plan,  # noqa: E402,F401
                     exp4_plan_chained, exp4_plan_sharded, exp4_relations_ref, merge_exp4, merge_shard_stats, num_buckets_exp1,
-                    num_distinct_sharded)
+                    num_distinct_sharded, star_plan_chained)

@@ -267,6 +267,42 @@ def exp4_plan_chained(ctx: Context, R, S, T, nb, keys=(0, 0), out=None, checksum
     return res
 
 
+def star_plan_chained(ctx: Context, R, builds, nb, keys, out=None, checksum: bool = True) -> dict:
+    """A k-way star Ndu from the separate operators, AlgNestJoinProbe / AlgUnnestHt stacked k deep
+    (algebra.hh:435-541; experiment 4 is k = 2): one nested table per (relation, key word) in `builds`
+    (an entry given twice shares its table: a self join), then probe(mainref) on R.keys[0], probe_refn
+    on each further R.keys[i] (its input is the previous level's survivors), then unnestn over the k
+    tables, all on the device. nb: the bucket count of every table, or one per build; keys: the R word
+    of each join attribute; out: a (cap, k + 1) int32 device tensor for the output rows
+    {r_row, row_1 .. row_k}. Returns Context.unnestn_result()'s dict plus the per-level lists
+    c_probe (tuples with a match) and c_probe_cmp (collision-chain comparisons)."""
+    import torch
+    k = len(builds)
+    if len(keys) != k:
+        raise ValueError("one R key word per build")
+    nbs = [nb] * k if isinstance(nb, int) else list(nb)
+    made, tables = {}, []
+    for (rel, kw), b in zip(builds, nbs):
+        ident = (id(rel), kw, b)
+        if ident not in made:
+            made[ident] = Table(ctx, HJ3D_NESTED, b)
+            made[ident].build(Rel(rel, key_word=kw))
+        tables.append(made[ident])
+    n = R.shape[0]
+    cur = torch.empty((max(n, 1), 2), dtype=torch.int32, device=R.device)
+    r = ctx.probe(tables[0], Rel(R, key_word=keys[0]), out=cur, mainref=True, checksum=False)
+    cur, c_probe, c_cmp = cur[:n], [r.n_matched], [r.n_cmps]
+    for i in range(1, k):
+        nxt = torch.empty((max(r.n_matched, 1), i + 2), dtype=torch.int32, device=R.device)
+        r = ctx.probe_refn(tables[i], Rel(R, key_word=keys[i]), cur, out=nxt, checksum=False)
+        cur = nxt[:r.n_out]
+        c_probe.append(r.n_matched)
+        c_cmp.append(r.n_cmps)
+    res = ctx.unnestn(tables, cur, out=out, checksum=checksum)
+    res.update(c_probe=c_probe, c_probe_cmp=c_cmp)
+    return res
+
+
 EXP4_SUM = ("c_probe_rs", "c_probe_rs_cmp", "c_probe_rt", "c_probe_rt_cmp", "c_unnest_1", "c_unnest_2", "c_top",
             "sum_a", "sum_b", "sum_c", "sum_h")
 

@@ -21,6 +21,8 @@
  *   hj3d_probe_ref             AlgNestJoinProbe::step driven by another AlgNestJoinProbe: the probe
  *                              input is stored nested tuples           algebra.hh:435-459,
  *                                                                     main_experiment4.cc:847-850
+ *   hj3d_probe_refn,           the two stacked to any depth up to HJ3D_NEST_MAX tables
+ *   hj3d_unnestn                                                       algebra.hh:435-541
  *   hj3d_table_stats          HtChaining1/HtNested1::makeStatistics  ht_chaining.hh:260-292,
  *                                                                     ht_nested.hh:450-482
  *   hj3d_table_clear           HtChaining1/HtNested1::clear           ht_chaining.hh:250-258,
@@ -426,6 +428,56 @@ hj3d_status hj3d_unnest2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* 
  * partitioner; otherwise the call waits for the stream once (the live count is read). */
 hj3d_status hj3d_probe_ref(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* base, const void* nested_dev,
                            uint64_t n, uint32_t in_words, uint32_t flags, void* out_dev, uint64_t out_cap);
+
+/* ---- wide nested tuples: the chain probe -> probe_refn -> .. -> unnestn over up to HJ3D_NEST_MAX tables ----
+ * AlgNestJoinProbe / AlgUnnestHt stack to any depth (algebra.hh:435-541); experiment 4 is the depth-2
+ * instance (main_experiment4.cc:435-466, 847-850). A stored nested tuple {a, ref_1 .. ref_k} carries at
+ * most HJ3D_NEST_MAX main refs. */
+#define HJ3D_NEST_MAX 6 /* main refs a stored nested tuple may carry */
+
+/* hj3d_probe_refn: hj3d_probe_ref for tuples of 1..HJ3D_NEST_MAX words {a, ref_1 .. ref_{in_words-1}}, so
+ * that its output (in_words + 1 <= 7 words) feeds it again. The contract is hj3d_probe_ref's, except:
+ * in_words ranges over 1 .. HJ3D_NEST_MAX (anything else: HJ3D_EINVAL); a tuple is live iff a is a row of
+ * base and none of its carried refs is 0xFFFFFFFF; every carried ref is opaque (copied, never
+ * dereferenced). Counters, checksums, overflow rule, asynchrony and result slot (hj3d_probe_result) are
+ * hj3d_probe_ref's; n_cmps is bit-exact. The output feeds hj3d_unnestn (k = in_words) or another
+ * hj3d_probe_refn. hj3d_probe_ref itself keeps refusing in_words > 2. */
+hj3d_status hj3d_probe_refn(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* base, const void* nested_dev,
+                            uint64_t n, uint32_t in_words, uint32_t flags, void* out_dev, uint64_t out_cap);
+
+/* Result of hj3d_unnestn over k tables; the counters follow the reference's order, in which the last
+ * table probed is unnested first (main_experiment4.cc:435-466). With |G_i| the group of a tuple's ref_i:
+ * c_unnest[j] (j < k) = the outputs of the (j + 1)-th unnest executed = sum over the live tuples of
+ * |G_k| * .. * |G_{k-j}|; entries j >= k are 0; c_top = c_unnest[k - 1]. For k = 2 these are
+ * hj3d_unnest2's c_unnest_1 / c_unnest_2. sum_row[i - 1] = the sum of row_i over the output rows. */
+typedef struct {
+  uint64_t n_in, n_live;            /* tuples given / tuples with every ref valid */
+  uint64_t c_unnest[HJ3D_NEST_MAX];
+  uint64_t c_top;
+  uint64_t sum_a, sum_row[HJ3D_NEST_MAX], sum_h, xor_h;
+} hj3d_unnestn_res;
+
+/* hj3d_unnestn: k stacked unnests (AlgUnnestHt::step, algebra.hh:490-541) as one operator, the k-table
+ * form of hj3d_unnest (k = 1) and hj3d_unnest2 (k = 2). nested_dev holds n tuples {u32 a, u32 ref_1 ..
+ * ref_k} of k + 1 words (4-byte aligned), ref_i a main ref of tables[i - 1]. Every table is HJ3D_NESTED;
+ * their geometries are free and a table may appear more than once (self joins). A tuple with any ref not
+ * below its table's current main-record count is skipped and no memory is read through it (the rule of
+ * hj3d_unnest, per table). Every other tuple yields {a, row_1 .. row_k} for each combination of the k
+ * groups' rows: with HJ3D_PROBE_EMIT as rows of 4 (k + 1) bytes to out_dev, at most out_cap of them, in
+ * no specified order; nothing is written at or beyond out_dev + 4 (k + 1) out_cap.
+ * The result goes to a slot of its own (hj3d_unnestn_result; the probe result slots are not touched):
+ * sum_a and sum_row always; with HJ3D_PROBE_CHECKSUM sum_h / xor_h fold h = pair(a, row_1), then
+ * h = mix64(h ^ row_i) for i = 2..k (the pair hash for k = 1, the triple hash for k = 2), else 0.
+ * hj3d_unnestn_result returns HJ3D_EOVERFLOW (with the complete counters) if c_top > out_cap under EMIT.
+ * Counts are exact while every tuple's product |G_1| * .. * |G_k| and c_top stay below 2^63; otherwise
+ * hj3d_unnestn_result returns HJ3D_EUNSUPPORTED (only n_in and n_live are set) and no output row was written.
+ * flags: HJ3D_PROBE_EMIT and HJ3D_PROBE_CHECKSUM only. HJ3D_EINVAL: any other flag, a null ctx / tables /
+ * entry of tables, a chaining table, k outside 1 .. HJ3D_NEST_MAX, n && !nested_dev, nested_dev or out_dev
+ * not 4-byte aligned, EMIT with out_dev == NULL and out_cap > 0, n >= 2^32; hj3d_unnestn_result before any
+ * hj3d_unnestn. Asynchronous; nested builds still pending are finished first, as by a probe. */
+hj3d_status hj3d_unnestn(hj3d_ctx* ctx, const hj3d_table* const* tables, uint32_t k, const void* nested_dev,
+                         uint64_t n, uint32_t flags, void* out_dev, uint64_t out_cap);
+hj3d_status hj3d_unnestn_result(hj3d_ctx* ctx, hj3d_unnestn_res* out);
 
 /* ---- multi-GPU exchange helpers (bucket-range radix partition) ----
  * Destination of a tuple: owner(bucket) = bucket * nparts / num_buckets. Writes (key,row)
