@@ -977,6 +977,52 @@ hj3d_status hj3d_unnestn_result(hj3d_ctx* ctx, hj3d_unnestn_res* out) {
   return HJ3D_OK;
 }
 
+hj3d_status hj3d_select_nested(hj3d_ctx* ctx, const void* nested_dev, uint64_t n, uint32_t k, const hj3d_rel* base,
+                               const hj3d_table* const* tables, const hj3d_rel* builds, const hj3d_nsel_pred* preds,
+                               uint32_t npred, uint32_t flags, void* out_dev, uint64_t out_cap) {
+  const char* const me = "hj3d_select_nested";
+  if (!ctx) return HJ3D_EINVAL;
+  if (k > HJ3D_NEST_MAX) return fail_in(ctx, me, "k must be 0 .. HJ3D_NEST_MAX");
+  if (npred > HJ3D_SEL_MAX || (npred && !preds)) return fail_in(ctx, me, "npred must be 0 .. HJ3D_SEL_MAX");
+  if (const hj3d_status st = unnest_flags_ok(ctx, me, flags); st != HJ3D_OK) return st;
+  if (base && (!rel_ok(base) || base->row_off != HJ3D_ROW_IMPLICIT))
+    return fail_in(ctx, me, "invalid base relation (implicit rows only)");
+  for (uint32_t i = 0; i < k; ++i) {
+    if (tables && tables[i] && tables[i]->desc.kind != HJ3D_NESTED) return fail_in(ctx, me, "needs nested tables");
+    if (builds && builds[i].stride && (!rel_ok(&builds[i]) || builds[i].row_off != HJ3D_ROW_IMPLICIT))
+      return fail_in(ctx, me, "invalid build relation (implicit rows only)");
+  }
+  for (uint32_t p = 0; p < npred; ++p) {
+    const hj3d_nsel_pred& q = preds[p];
+    if (q.source > HJ3D_NSEL_FIRST) return fail_in(ctx, me, "unknown predicate source");
+    const hj3d_rel* rel = nullptr;  // the relation whose word the predicate reads
+    if (q.source == HJ3D_NSEL_BASE) {
+      if (q.slot != 0) return fail_in(ctx, me, "a BASE predicate's slot must be 0");
+      if (!(rel = base)) return fail_in(ctx, me, "a BASE predicate without base");
+    } else {
+      if (q.slot < 1 || q.slot > k) return fail_in(ctx, me, "a predicate's slot outside 1 .. k");
+      if (!tables || !tables[q.slot - 1]) return fail_in(ctx, me, "a COUNT / FIRST predicate without its table");
+      if (q.source == HJ3D_NSEL_FIRST && !(builds && builds[q.slot - 1].stride))
+        return fail_in(ctx, me, "a FIRST predicate without its build relation");
+      if (q.source == HJ3D_NSEL_FIRST) rel = &builds[q.slot - 1];
+    }
+    if (rel ? !sel_ok(rel, &q.pred, 1) : q.pred.op > HJ3D_SEL_RANGE) return fail_in(ctx, me, "invalid predicate");
+  }
+  if ((n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32)) return fail_in(ctx, me, "invalid input");
+  if (uintptr_t(out_dev) & 3) return fail_in(ctx, me, "misaligned output buffer");
+  if (const hj3d_status st = emit_buffer_ok(ctx, me, flags, out_dev, out_cap); st != HJ3D_OK) return st;
+  for (uint32_t i = 0; tables && i < k; ++i)
+    if (tables[i])
+      if (hipError_t re = resolve(ctx, tables[i]); re != hipSuccess) return from_hip(ctx, re, me);
+  PhaseTimer tm(ctx, HJ3D_T_PROBE);
+  hipError_t e = select_nested(ctx, nested_dev, n, k, base, tables, builds, preds, npred, flags, out_dev, out_cap,
+                               ctx->res.as<uint64_t>(), ctx->stream);
+  // the non-dense overflow convention: n_out against the capacity, on the stream
+  if (e == hipSuccess) e = out_check(ctx, false, flags, out_cap);
+  note_probe(ctx, false, flags, n, out_cap);
+  return from_hip(ctx, e, me);
+}
+
 hj3d_status hj3d_probe_geometry(hj3d_ctx* ctx, uint64_t nb_local, uint64_t n_build, uint32_t out[5]) {
   if (!ctx || !out || nb_local == 0 || nb_local >= (1ull << 32)) return HJ3D_EINVAL;
   const PkPlan pl = pk_plan(ctx, uint32_t(nb_local), n_build);

@@ -472,6 +472,14 @@ hipError_t probe_refn_compact(hj3d_ctx* ctx, const hj3d_table* t, const uint2* d
 // (res: the kUnnWords words of ctx->resn, cleared here)
 hipError_t unnest_wide(hj3d_ctx* ctx, const hj3d_table* const* tables, uint32_t k, const void* in, uint64_t n,
                        uint32_t flags, void* out, uint64_t out_cap, uint64_t* res_dev, hipStream_t s);
+// select_nested.hip: hj3d_select_nested's two kernels (k_nsel_flags, k_nsel_write) around a scan of the
+// tile counts: n tuples {a, ref_1 .. ref_k} compacted to the live ones that pass the predicates, in input
+// order (validated arguments, resolved tables; base / tables / builds and their entries nullable;
+// clears res, the probe result slot, itself). Uses scratch kScrC (pass masks) and kScrD (tile counts).
+hipError_t select_nested(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t k, const hj3d_rel* base,
+                         const hj3d_table* const* tables, const hj3d_rel* builds, const hj3d_nsel_pred* preds,
+                         uint32_t npred, uint32_t flags, void* out, uint64_t out_cap, uint64_t* res_dev,
+                         hipStream_t s);
 // exp4.hip
 hipError_t probe2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const hj3d_rel& r, uint32_t flags,
                   void* out, uint64_t out_cap, uint64_t* res_dev, hipStream_t s);

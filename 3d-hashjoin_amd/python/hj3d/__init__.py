@@ -35,6 +35,7 @@ OPT_DIAG_GBAR = 16
 OPT_DIAG_LOOKBACK = 17
 SEL_LT, SEL_LE, SEL_GT, SEL_GE, SEL_EQ, SEL_NE, SEL_RANGE = range(7)
 SEL_MAX = 4
+NSEL_BASE, NSEL_COUNT, NSEL_FIRST = range(3)  # where a nested-tuple predicate takes its u32 (select_nested)
 SEL_OPS = {"<": SEL_LT, "<=": SEL_LE, ">": SEL_GT, ">=": SEL_GE, "==": SEL_EQ, "!=": SEL_NE, "range": SEL_RANGE}
 
 MASK64 = (1 << 64) - 1
@@ -76,6 +77,10 @@ class _UnnestNRes(C.Structure):
 class _SelPred(C.Structure):
     _fields_ = [("word_off", C.c_uint32), ("op", C.c_uint32), ("is_signed", C.c_uint32), ("reserved", C.c_uint32),
                 ("lo", C.c_int64), ("hi", C.c_int64)]
+
+
+class _NSelPred(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("slot", C.c_uint32), ("pred", _SelPred)]
 
 
 class _Stats(C.Structure):
@@ -157,6 +162,7 @@ def lib():
         "hj3d_bitmap_or_popcount": (st, [p, p, u32, u64, p]),
         "hj3d_select": (st, [p, R, C.POINTER(_SelPred), u32, p, p]),
         "hj3d_probe_sel": (st, [p, p, R, C.POINTER(_SelPred), u32, u32, p, u64]),
+        "hj3d_select_nested": (st, [p, p, u64, u32, R, C.POINTER(p), R, C.POINTER(_NSelPred), u32, u32, p, u64]),
         "hj3d_gen_keys": (st, [p, p, u64, u32, u32, u64, u64, u64]),
         "hj3d_gen_fk": (st, [p, p, u64, u32, u32, u64, u32, u64]),
         "hj3d_gen_zipf": (st, [p, p, u64, u32, u32, u64, u32, C.c_double, u64]),
@@ -569,6 +575,41 @@ class Context:
                                          ptr, cap), "hj3d_probe_sel")
         return self.probe_result() if fetch else None
 
+    # ---- selection between the nested probe and the unnest (AlgSelection over stored nested tuples) ----
+    def select_nested(self, nested, preds, base: Optional[Rel] = None, tables=None, builds=None, out=None,
+                      checksum: bool = True, fetch: bool = True) -> Optional[ProbeResult]:
+        """hj3d_select_nested: the live tuples of `nested` (a contiguous (n, k + 1) int32 device tensor of
+        {a, ref_1 .. ref_k}, 0 <= k <= HJ3D_NEST_MAX) that pass every predicate, in input order.
+        preds: ("base", word, op, lo[, hi][, signed]) compares a word of base row a; ("count", slot, op,
+        lo[, hi]) the size of the group ref_slot names in tables[slot - 1]; ("first", slot, word, op,
+        lo[, hi][, signed]) a word of that group's first build tuple in builds[slot - 1]. op in SEL_OPS;
+        compared as int32 unless signed=False (count: as uint32). base: the Rel a is a row of (implicit
+        rows); tables / builds: lists of k Tables / Rels, entries or the whole list None where no
+        predicate needs them (a ref without its table is only compared with 0xFFFFFFFF). A tuple is dead,
+        and dropped, when a is outside base, a ref is 0xFFFFFFFF or not below its table's main-record
+        count, or a "first" row lies outside its build relation. out: a contiguous (cap, k + 1) int32
+        device tensor that receives the first cap passing tuples (None: counters only). Result: n_probe
+        = n, n_matched = live tuples, n_out = passing tuples, sum_a over them, sum_h / xor_h their row
+        hashes (checksum=True); `overflow` tells whether some did not fit."""
+        torch = _torch()
+        if not nested.is_cuda or nested.dtype not in (torch.int32, torch.uint32) or nested.dim() != 2 or \
+                not 1 <= nested.shape[1] <= HJ3D_NEST_MAX + 1 or not nested.is_contiguous():
+            raise ValueError(f"nested must be a contiguous (n, 1..{HJ3D_NEST_MAX + 1}) int32 device tensor")
+        k = nested.shape[1] - 1
+        if len(preds) > SEL_MAX:
+            raise ValueError(f"at most {SEL_MAX} predicates")
+        for what, lst in (("tables", tables), ("builds", builds)):
+            if lst is not None and len(lst) != k:
+                raise ValueError(f"{what} must have one entry per ref ({k}) or be None")
+        ptr_in, n = _words(nested, k + 1, "nested")
+        emit, ptr, cap = _emit_args(out, k + 1)
+        flags = (PROBE_CHECKSUM if checksum else 0) | emit
+        th = None if tables is None else (C.c_void_p * max(k, 1))(*[None if t is None else t.h for t in tables])
+        rs = None if builds is None else (_Rel * max(k, 1))(*[_Rel() if r is None else r.c for r in builds])
+        self._check(lib().hj3d_select_nested(self.h, ptr_in, n, k, None if base is None else C.byref(base.c), th, rs,
+                                             _nsel_preds(preds), len(preds), flags, ptr, cap), "hj3d_select_nested")
+        return self.probe_result() if fetch else None
+
     def packed_probe(self, on: bool = True):
         """A/B switch: the unique chaining probe on packed pairs (default) or on (hash, row) pairs."""
         self.set_option(OPT_PACKED_PROBE, int(on))
@@ -736,6 +777,25 @@ def _sel_preds(preds):
         hi = pr[3] if len(pr) > 3 and pr[3] is not None else 0
         signed = pr[4] if len(pr) > 4 else True
         arr[k] = _SelPred(4 * word, SEL_OPS.get(op, op), int(bool(signed)), 0, int(lo), int(hi))
+    return arr
+
+
+def _nsel_preds(preds):
+    """hj3d_nsel_pred array of ("base", word, op, lo[, hi][, signed]) / ("count", slot, op, lo[, hi]) /
+    ("first", slot, word, op, lo[, hi][, signed]) tuples."""
+    arr = (_NSelPred * max(1, len(preds)))()
+    for i, pr in enumerate(preds):
+        kind = pr[0]
+        if kind == "base":
+            src, slot, rest = NSEL_BASE, 0, pr[1:]
+        elif kind == "count":
+            # |G| is a u32: word 0 (unused), op, lo, hi, unsigned
+            src, slot, rest = NSEL_COUNT, pr[1], (0, pr[2], pr[3], pr[4] if len(pr) > 4 else None, False)
+        elif kind == "first":
+            src, slot, rest = NSEL_FIRST, pr[1], pr[2:]
+        else:
+            raise ValueError(f"unknown predicate source {kind!r} (base, count, first)")
+        arr[i] = _NSelPred(src, int(slot), _sel_preds([rest])[0])
     return arr
 
 

@@ -267,7 +267,7 @@ def exp4_plan_chained(ctx: Context, R, S, T, nb, keys=(0, 0), out=None, checksum
     return res
 
 
-def star_plan_chained(ctx: Context, R, builds, nb, keys, out=None, checksum: bool = True) -> dict:
+def star_plan_chained(ctx: Context, R, builds, nb, keys, out=None, checksum: bool = True, filters=None) -> dict:
     """A k-way star Ndu from the separate operators, AlgNestJoinProbe / AlgUnnestHt stacked k deep
     (algebra.hh:435-541; experiment 4 is k = 2): one nested table per (relation, key word) in `builds`
     (an entry given twice shares its table: a self join), then probe(mainref) on R.keys[0], probe_refn
@@ -275,7 +275,11 @@ def star_plan_chained(ctx: Context, R, builds, nb, keys, out=None, checksum: boo
     tables, all on the device. nb: the bucket count of every table, or one per build; keys: the R word
     of each join attribute; out: a (cap, k + 1) int32 device tensor for the output rows
     {r_row, row_1 .. row_k}. Returns Context.unnestn_result()'s dict plus the per-level lists
-    c_probe (tuples with a match) and c_probe_cmp (collision-chain comparisons)."""
+    c_probe (tuples with a match) and c_probe_cmp (collision-chain comparisons).
+    filters: {level: preds}, a selection (AlgSelection, algebra.hh:278-358) stacked on level i's probe
+    (0-based): Context.select_nested over that level's output, with R as base and the tables and build
+    relations so far; the next level (or the unnest) sees only the passing tuples. The result then
+    gains c_select, the passing tuples per level (None where a level has no filter)."""
     import torch
     k = len(builds)
     if len(keys) != k:
@@ -291,15 +295,31 @@ def star_plan_chained(ctx: Context, R, builds, nb, keys, out=None, checksum: boo
     n = R.shape[0]
     cur = torch.empty((max(n, 1), 2), dtype=torch.int32, device=R.device)
     r = ctx.probe(tables[0], Rel(R, key_word=keys[0]), out=cur, mainref=True, checksum=False)
-    cur, c_probe, c_cmp = cur[:n], [r.n_matched], [r.n_cmps]
+    cur, c_probe, c_cmp, c_select = cur[:n], [r.n_matched], [r.n_cmps], []
+
+    def selected(level, cur, live):
+        """Level `level`'s output behind its filter: (tuples, an upper bound of the live ones among them)."""
+        if filters is None or level not in filters:
+            c_select.append(None)
+            return cur, live
+        kept = torch.empty((max(live, 1), level + 2), dtype=torch.int32, device=R.device)
+        s = ctx.select_nested(cur, filters[level], base=Rel(R, key_word=keys[level]), tables=tables[:level + 1],
+                              builds=[Rel(rel, key_word=kw) for rel, kw in builds[:level + 1]], out=kept, checksum=False)
+        c_select.append(s.n_out)
+        return kept[:s.n_out], s.n_out
+
+    cur, live = selected(0, cur, r.n_matched)
     for i in range(1, k):
-        nxt = torch.empty((max(r.n_matched, 1), i + 2), dtype=torch.int32, device=R.device)
+        nxt = torch.empty((max(live, 1), i + 2), dtype=torch.int32, device=R.device)
         r = ctx.probe_refn(tables[i], Rel(R, key_word=keys[i]), cur, out=nxt, checksum=False)
         cur = nxt[:r.n_out]
         c_probe.append(r.n_matched)
         c_cmp.append(r.n_cmps)
+        cur, live = selected(i, cur, r.n_out)
     res = ctx.unnestn(tables, cur, out=out, checksum=checksum)
     res.update(c_probe=c_probe, c_probe_cmp=c_cmp)
+    if filters is not None:
+        res["c_select"] = c_select
     return res
 
 

@@ -29,6 +29,9 @@
  *                                                                     ht_nested.hh:438-447
  *   hj3d_select                AlgSelection / AlgDynSelection::step   algebra.hh:278-358
  *   hj3d_probe_sel             AlgScan -> AlgSelection -> AlgHashJoinProbe / AlgNestJoinProbe
+ *   hj3d_select_nested         AlgSelection / AlgDynSelection::step between AlgNestJoinProbe and
+ *                              AlgUnnestHt, over stored nested tuples   algebra.hh:278-358 on 435-459,
+ *                                                                     main_algebra_example.cc:226-234, 305-316
  *
  * Semantics kept bit-exact with the reference: hash = murmur3 fmix32 (util/hasht.hh:52-61),
  * bucket = hash % num_buckets, and every counter the reference reports (match counts,
@@ -630,6 +633,60 @@ hj3d_status hj3d_select(hj3d_ctx* ctx, const hj3d_rel* rel, const hj3d_sel_pred*
  * and needs out_cap >= probe->n. */
 hj3d_status hj3d_probe_sel(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* probe, const hj3d_sel_pred* preds,
                            uint32_t npred, uint32_t flags, void* out_dev, uint64_t out_cap);
+
+/* ---- selection over stored nested tuples ----
+ * hj3d_select_nested replaces AlgSelection / AlgDynSelection::step (algebra.hh:278-358) stacked on an
+ * AlgNestJoinProbe (algebra.hh:435-459), i.e. a selection between the nested probe and the unnest
+ * (main_algebra_example.cc:226-234, 305-316): it forwards, in scan order, the stored nested tuples whose
+ * predicate holds. A predicate compares one u32 taken from the tuple's base row, from the size of one
+ * of its groups, or from the first build tuple of one of its groups (the reference reads both through
+ * MainNode). */
+/* where a nested-tuple predicate takes the u32 it compares */
+enum { HJ3D_NSEL_BASE = 0,   /* word at pred.word_off of the base tuple whose row id is a          */
+       HJ3D_NSEL_COUNT = 1,  /* |G_slot|: sub_len of main record ref_slot of tables[slot - 1]     */
+       HJ3D_NSEL_FIRST = 2 };/* word at pred.word_off of the tuple of builds[slot - 1] whose row is
+                                that main record's first build row (MainNode::data())             */
+typedef struct {
+  uint32_t source;      /* HJ3D_NSEL_*                                   */
+  uint32_t slot;        /* COUNT / FIRST: 1..k; BASE: 0                  */
+  hj3d_sel_pred pred;   /* op, is_signed, lo, hi as hj3d_select; word_off unused (0) for COUNT */
+} hj3d_nsel_pred;
+/* nested_dev: n stored nested tuples {u32 a, u32 ref_1 .. ref_k} of k + 1 words (4-byte aligned),
+ * 0 <= k <= HJ3D_NEST_MAX: every width the family produces ({a}, a HJ3D_PROBE_MAINREF probe's dense
+ * output as it stands, hj3d_probe_refn's output of up to 7 words). base (the relation a is a row of),
+ * tables (k entries, ref_i a main ref of tables[i - 1]) and builds (k entries, builds[i - 1] the relation
+ * tables[i - 1] was built from) may be NULL, and so may an entry of tables; an entry of builds with
+ * stride 0 counts as not given. A predicate whose source object is missing (BASE without base, COUNT
+ * without its table, FIRST without its table or build relation) is HJ3D_EINVAL.
+ * A tuple is dead iff base is given and a is not a row of it (implicit rows: tuple index
+ * a - base->row_base), or any ref is 0xFFFFFFFF, or a ref whose table is given is not below that table's
+ * current main-record count (the rule of hj3d_unnest), or a FIRST predicate's first build row is not a
+ * row of its build relation. Dead tuples are dropped, as AlgNestJoinProbe passes nothing downstream
+ * without a match; no memory is read through a dead tuple. A ref whose table is not given is opaque:
+ * compared with 0xFFFFFFFF and copied. With npred == 0 the operator is this compaction alone.
+ * The predicate is the conjunction of npred <= HJ3D_SEL_MAX predicates, each evaluated as hj3d_select
+ * evaluates its own (int32 or uint32 compare of the source word against lo, or lo <= v < hi); COUNT
+ * compares the u32 sub_len. Each embedded hj3d_sel_pred must be valid for its relation (word_off a
+ * multiple of 4 inside the tuple, a known op).
+ * With HJ3D_PROBE_EMIT the passing tuples are written unchanged, k + 1 words each, IN INPUT ORDER
+ * (AlgSelection forwards in scan order, algebra.hh:295-300; hj3d_select is stable too), at most out_cap
+ * of them: when more pass, the first out_cap passing tuples are the ones written. Nothing is written at
+ * or beyond out_dev + 4 (k + 1) out_cap. nested_dev and out_dev must not overlap.
+ * Result (the probe result slot, hj3d_probe_result): n_probe = n, n_matched = live tuples, n_out =
+ * passing tuples, n_cmps = 0, sum_a = the sum of a over the passing tuples (always); with
+ * HJ3D_PROBE_CHECKSUM sum_h / xor_h fold h = mix64(a) for k = 0, else h = pair(a, ref_1), then
+ * h = mix64(h ^ ref_i) for i = 2..k (else 0); sum_b = sum_c = 0. HJ3D_EOVERFLOW (complete counters) if
+ * n_out > out_cap under EMIT.
+ * flags: HJ3D_PROBE_EMIT and HJ3D_PROBE_CHECKSUM only. HJ3D_EINVAL: any other flag, a null ctx, k above
+ * HJ3D_NEST_MAX, npred above HJ3D_SEL_MAX (or npred && !preds), a slot outside 1..k (BASE: not 0), an
+ * unknown source or op, a chaining table, an invalid base or build relation or one with explicit rows,
+ * nested_dev or out_dev not 4-byte aligned, n && !nested_dev, EMIT with out_dev == NULL and out_cap > 0,
+ * n >= 2^32. Asynchronous on the context stream; pending nested builds of the given tables are finished
+ * first, as by a probe. */
+hj3d_status hj3d_select_nested(hj3d_ctx* ctx, const void* nested_dev, uint64_t n, uint32_t k,
+                               const hj3d_rel* base, const hj3d_table* const* tables, const hj3d_rel* builds,
+                               const hj3d_nsel_pred* preds, uint32_t npred,
+                               uint32_t flags, void* out_dev, uint64_t out_cap);
 
 /* ---- synthetic key/FK relations generated on the device (bench / full-size checks) ----
  * R.k = a seeded bijective permutation of [0, n_keys) (keys for global rows
