@@ -8,7 +8,9 @@
 //               {v, row} with v = (b - p*W) << qbits | h / NB to the workgroup's region of slice p.
 //               The bucket and the quotient determine h (h = (h / NB) * NB + b), so the probe needs
 //               neither a modulo nor a division per tuple. Regions are written in whole 128-B
-//               segments (runs shorter than a segment ride in registers to the next tile).
+//               segments (up to 1024 slices: each slice gathers its segment in an LDS window that
+//               lasts the whole workgroup; beyond: per-tile stage, runs shorter than a segment ride
+//               in registers to the next tile).
 //   k_pk_probe  one 1024-thread workgroup per slice (or share of its regions): stages the slice
 //               (directory + entries, entry hashes turned into quotients) in LDS, reserves its
 //               output range with one atomic, probes every pair against LDS in the reference's
@@ -30,19 +32,19 @@ namespace {
 constexpr int kPkBlock = 1024;
 // Tunables, fixed by the sweeps recorded in DESIGN.md 4.1 (the losing variants are gone from the
 // source): 8192-tuple tiles (4096: 0.556 ms, 8192: 0.466 ms for k_pk_part at config B), the next tile's
-// keys loaded once the stage is built (two tiles ahead spilled), 128-B region segments (64-B: slower in
-// both kernels), non-temporal key loads (0.447 -> 0.436 ms) and region stores (0.452 -> 0.447 ms),
-// five barriers per tile, guarded key loads and rank atomics (the clamped form was not faster).
+// keys in flight across the write-out, 128-B region segments (64-B: slower in both kernels),
+// non-temporal key loads (0.447 -> 0.436 ms) and region stores (0.452 -> 0.447 ms), guarded key loads
+// and rank atomics (the clamped form was not faster). Stage form: the next tile's keys loaded once
+// the stage is built (two tiles ahead spilled), five barriers per tile.
 constexpr int kPkRounds = 8;
 constexpr int kPkTile = kPkBlock * kPkRounds;
 constexpr int kPkTBits = 32 - __builtin_clz(uint32_t(kPkTile - 1));  // bits of a rank inside the tile
 constexpr uint32_t kPkSeg = 16;                                     // pairs per region segment (128 B)
-constexpr uint32_t kPkStage = 17408;  // LDS stage (pairs): the tile + the carried pairs (< kPkSeg per slice)
-static_assert(kPkTile <= kPkStage && kPkStage < 65536, "the tile alone fits the stage; stage offsets in 16 bits");
-// the stage of the two-slices-per-thread form (64-B segments: carries of < 8 pairs, ~3.5 on average per
-// slice, so the tile and ~7 K carried pairs; with its 16 KB of slice words and 15.5 KB of segment
-// words it fills the LDS)
+// the LDS stage (pairs) of the two-slices-per-thread form (64-B segments: carries of < 8 pairs, ~3.5 on
+// average per slice, so the tile and ~7 K carried pairs; with its 16 KB of slice words and 15.5 KB of
+// segment words it fills the LDS)
 constexpr uint32_t kPkStage2 = 15872;
+static_assert(kPkTile <= kPkStage2 && kPkStage2 < 65536, "the tile alone fits the stage; stage offsets in 16 bits");
 constexpr uint32_t kPkMaxP1 = 2 * kPkBlock;  // slices one partition level takes (two per thread)
 constexpr uint32_t kSortedMaxPk = 32;
 constexpr uint32_t kOvfFlag = 0x80000000u;
@@ -65,11 +67,14 @@ __device__ __forceinline__ void pk_ovf_append(bool me, uint2 e, uint2* __restric
 }
 
 // ---- k_pk_part: the probe relation -> packed pairs in per-(workgroup, slice) regions ----
-// Regions: region[(g * P + p) * cap + k], counts[g * P + p] pairs. PPT slices per thread (P <= 1024
-// PPT): thread t carries slices t + k * 1024's leftover pairs (< one segment each) in registers. PPT = 1:
-// 128-B segments; PPT = 2 (1024 < P <= 2048, one partition level instead of two: config D's
-// 2.5e7-bucket rank at 4 GPUs): 64-B segments, a smaller carry and stage. SEL: a one-word selection
-// fused in.
+// Regions: region[(g * P + p) * cap + k], counts[g * P + p] pairs: whole segments, then one partial
+// tail. PPT slices per thread (P <= 1024 PPT). PPT = 1: 128-B segments, the window form
+// (pk_part_windows, below). PPT = 2 (1024 < P <= 2048, one partition level instead of two: config D's
+// 2.5e7-bucket rank at 4 GPUs): 64-B segments, the stage form (pk_part_stage): thread t carries slices
+// t + k * 1024's leftover pairs (< one segment each) in registers, and every tile's runs are laid out
+// in an LDS stage behind them (its windows would not fit beside a 2048-entry list). SEL: a one-word
+// selection fused in.
+// The stage form:
 // Memory ordering: vmcnt counts loads and stores together, in issue order, so a load can only be
 // waited for together with every older store. The next tile's keys are loaded right after this tile's
 // stage is built (loading two tiles ahead, so that the wait would never cover this tile's region
@@ -77,13 +82,13 @@ __device__ __forceinline__ void pk_ovf_append(bool me, uint2 e, uint2* __restric
 template <int PPT>
 struct PkPartGeom {
   static constexpr uint32_t kSeg = kPkSeg / PPT;                          // pairs per region segment
-  static constexpr uint32_t kStage = PPT == 1 ? kPkStage : kPkStage2;      // LDS stage (pairs)
+  static constexpr uint32_t kStage = kPkStage2;                            // LDS stage (pairs)
 };
 template <bool IMPLICIT, bool SEL, int PPT>
-__global__ __launch_bounds__(kPkBlock) void k_pk_part(RelView r, PkGeom pk, uint32_t ntiles, uint32_t cap,
-                                                      uint2* __restrict__ region, uint32_t* __restrict__ counts,
-                                                      uint2* __restrict__ ovf, uint64_t* __restrict__ ctl,
-                                                      SelRange sel, uint32_t stage_lim) {
+__device__ __forceinline__ void pk_part_stage(const RelView& r, const PkGeom& pk, uint32_t ntiles, uint32_t cap,
+                                              uint2* __restrict__ region, uint32_t* __restrict__ counts,
+                                              uint2* __restrict__ ovf, uint64_t* __restrict__ ctl,
+                                              const SelRange& sel, uint32_t stage_lim) {
   constexpr uint32_t SEG = PkPartGeom<PPT>::kSeg, STAGE = PkPartGeom<PPT>::kStage;
   __shared__ uint2 stage[STAGE];
   __shared__ uint32_t loc[kPkBlock * PPT];
@@ -297,6 +302,215 @@ __global__ __launch_bounds__(kPkBlock) void k_pk_part(RelView r, PkGeom pk, uint
   } else {
     if (blockIdx.x == 0 && me == 0) atomicAdd(reinterpret_cast<unsigned long long*>(ctl + kCtlNprobe), (unsigned long long)n);
   }
+}
+
+// The window form (one slice per thread, P <= 1024): software write-combining. Every slice keeps a
+// window of one segment in LDS for the whole workgroup (win[p], kPkSeg slots and a pad slot;
+// fill[p] pairs in it), so nothing is carried in registers and no stage is laid out per tile.
+// Per tile: every item takes its position in its slice's window with one LDS atomic,
+// pos = fill[p]++; its slot is pos % kPkSeg and its round pos / kPkSeg, and the pair waits in
+// registers until its round. Round 0 writes its slots; then, per round: thread p lists its window if
+// it is whole ({region index of the slice's cursor, p}, or {kOvfFlag | p, p} once the region is full),
+// takes kPkSeg off fill[p] and votes for another round if a whole segment is still to come; the
+// listed windows are written out, kPkSeg consecutive lanes per segment; the round's items write their
+// slots. Three barriers per tile unless some slice received more than two segments' worth.
+// A slice whose region is full is closed (kWinClosed in fill[p]): its pairs then go from registers
+// straight to the overflow list, so a hot key costs rounds only until its region is full.
+// Only whole segments reach a region before the workgroup's end, so the cursors stay multiples of
+// kPkSeg; the windows' leftovers (< kPkSeg pairs) follow at the end as the region's partial tail.
+constexpr uint32_t kWinSlots = kPkSeg + 1;  // the pad slot spreads the slices' windows over the banks
+constexpr uint32_t kWinPosBits = 14;        // a position: the window's fill (< kPkSeg) + the tile's pairs
+constexpr uint32_t kWinClosed = 0x80000000u;
+static_assert(kPkTile + kPkSeg <= (1u << kWinPosBits) && kPkBlock <= (1u << (31 - kWinPosBits)), "slice and position in one word");
+static_assert(kPkBlock * kWinSlots * sizeof(uint2) + kPkBlock * (sizeof(uint32_t) + sizeof(uint2)) + 64 <= 160 * 1024,
+              "windows, fills and the flush list fit the LDS");
+template <bool IMPLICIT, bool SEL>
+__device__ __forceinline__ void pk_part_windows(const RelView& r, const PkGeom& pk, uint32_t ntiles, uint32_t cap,
+                                                uint2* __restrict__ region, uint32_t* __restrict__ counts,
+                                                uint2* __restrict__ ovf, uint64_t* __restrict__ ctl,
+                                                const SelRange& sel) {
+  __shared__ uint2 win[kPkBlock * kWinSlots];
+  __shared__ uint32_t fill[kPkBlock];
+  __shared__ uint2 flist[kPkBlock];  // windows to write out this round: a slice lists at most one
+  __shared__ uint32_t nlist, anyclosed;
+  const uint32_t me = threadIdx.x, P = pk.P, n = uint32_t(r.n);
+  const int lane = threadIdx.x & 63;
+  const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  // thread p's slice: its region (host: G * P * cap < 2^31) and the pairs the region has taken
+  const uint32_t my_reg = (blockIdx.x * P + (me < P ? me : 0u)) * cap;
+  uint32_t my_cur = 0;
+  constexpr int NS = SEL ? kPkRounds : 1, NW = IMPLICIT ? 1 : kPkRounds;
+  uint32_t ha[kPkRounds], pa[NS], wa[NW];  // this tile's keys (then packed words), selection words, rows
+  uint32_t hn[kPkRounds], pn[NS], wn[NW];  // the next tile's
+  auto load = [&](uint32_t (&h)[kPkRounds], uint32_t (&pw)[NS], uint32_t (&rw)[NW], uint32_t tile)
+                  __attribute__((always_inline)) {
+    const uint32_t base = tile * kPkTile;
+#pragma unroll
+    for (int j = 0; j < kPkRounds; ++j) {
+      const uint32_t i = base + uint32_t(j) * kPkBlock + me;
+      const char* t = r.base + uint64_t(i) * r.stride;
+      h[j] = i < n ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(t + r.key_off)) : 0u;
+      if constexpr (!IMPLICIT)
+        rw[j] = i < n ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(t + r.row_off)) : 0u;
+      if constexpr (SEL) pw[j] = i < n ? *reinterpret_cast<const uint32_t*>(t + sel.word_off) : 0u;
+    }
+  };
+  auto to_ovf = [&](uint2 e, uint32_t p, bool me_) __attribute__((always_inline)) {  // packed pair of slice p -> {h, row}
+    pk_ovf_append(me_, make_uint2(pk.hash_of(e.x, p), e.y), ovf, ctl);
+  };
+  fill[me] = 0;
+  if (me == 0) {
+    nlist = 0;
+    anyclosed = 0;
+  }
+  __syncthreads();
+  uint32_t npassed = 0;
+  load(ha, pa, wa, blockIdx.x);
+  for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const uint32_t base = tile * kPkTile;
+    const uint32_t rb = IMPLICIT ? uint32_t(r.row_base) + base : 0u;
+    const auto pair_of = [&](int j) __attribute__((always_inline)) {
+      uint32_t row;
+      if constexpr (IMPLICIT) row = rb + uint32_t(j) * kPkBlock + me;
+      else row = wa[j];
+      return make_uint2(ha[j], row);
+    };
+    // hash, bucket, slice, position in the slice's window: rk = slice << kWinPosBits | position
+    // (kInvalid: no pair, or already written); shut: bit j set if item j met a closed slice
+    uint32_t rk[kPkRounds], shut = 0;
+    constexpr uint32_t kPosMask = (1u << kWinPosBits) - 1;
+#pragma unroll
+    for (int j = 0; j < kPkRounds; ++j) {
+      const uint32_t i = base + uint32_t(j) * kPkBlock + me;
+      const uint32_t hv = murmur32(ha[j]);
+      const uint32_t q = pk.dnb.div(hv);
+      const uint32_t bl = hv - q * pk.nb - pk.lo;
+      bool pass = i < n;
+      if constexpr (SEL) {
+        pass = pass && sel.test(pa[j]);
+        npassed += pass;
+      }
+      const bool ok = pass && bl < pk.nbl;
+      rk[j] = kInvalid;
+      if (ok) {
+        const uint32_t p = pk.dw.div(bl);
+        ha[j] = ((bl - p * pk.W) << pk.qbits) | q;  // the packed pair's first word
+        const uint32_t pos = atomicAdd(&fill[p], 1u);
+        rk[j] = (p << kWinPosBits) | (pos & kPosMask);
+        shut |= (pos >> 31) << j;
+      }
+    }
+    // round 0 fills the windows up; pairs of closed slices leave for the overflow list
+#pragma unroll
+    for (int j = 0; j < kPkRounds; ++j) {
+      const bool v = rk[j] != kInvalid, cl = (shut >> j) & 1u;
+      const uint32_t p = rk[j] >> kWinPosBits, pos = rk[j] & kPosMask;
+      const uint2 e = pair_of(j);
+      if (v && !cl && pos < kPkSeg) win[p * kWinSlots + pos] = e;
+      to_ovf(e, p, v && cl);
+      if (cl || pos < kPkSeg) rk[j] = kInvalid;
+    }
+    load(hn, pn, wn, tile + gridDim.x);  // the next tile (keys past the end load nothing)
+    __syncthreads();
+    uint32_t f = fill[me];  // only thread p changes fill[p] until the next tile's atomics
+    for (uint32_t rnd = 1;; ++rnd) {
+      // thread p: a whole window is listed for the write-out, or closes the slice if its region is full
+      const bool seg = !(f & kWinClosed) && f >= kPkSeg;
+      const bool fit = my_cur + kPkSeg <= cap;
+      bool more = false;
+      if (seg) {
+        f = fit ? f - kPkSeg : kWinClosed;
+        fill[me] = f;
+        more = fit && f >= kPkSeg;
+        if (!fit) anyclosed = 1;
+      }
+      const uint64_t m = __ballot(seg);
+      if (m) {
+        const int leader = __ffsll((unsigned long long)m) - 1;
+        uint32_t b = 0;
+        if (lane == leader) b = atomicAdd(&nlist, uint32_t(__popcll(m)));
+        b = __shfl(b, leader, kWave);
+        if (seg) flist[b + uint32_t(__popcll(m & lt))] = make_uint2(fit ? my_reg + my_cur : (kOvfFlag | me), me);
+      }
+      if (seg && fit) my_cur += kPkSeg;
+      const bool again = __syncthreads_or(more);
+      // the listed windows: kPkSeg consecutive lanes store one segment
+      const uint32_t nl = nlist;
+      const bool anycl = anyclosed != 0;
+      for (uint32_t kk = me; kk < nl * kPkSeg; kk += kPkBlock) {
+        const uint2 si = flist[kk / kPkSeg];
+        const uint32_t j = kk % kPkSeg;
+        const uint2 e = win[si.y * kWinSlots + j];
+        const bool spill = si.x & kOvfFlag;
+        if (!spill)
+          __builtin_nontemporal_store((uint64_t(e.y) << 32) | e.x, reinterpret_cast<uint64_t*>(region + si.x + j));
+        to_ovf(e, si.y, spill);
+      }
+      __syncthreads();
+      if (me == 0) nlist = 0;
+      // this round's items take their slots in the emptied windows. No barrier follows the last
+      // round: its slots lie below the new fill and the next tile's round 0 goes at or above it.
+      if (!anycl) {
+#pragma unroll
+        for (int j = 0; j < kPkRounds; ++j) {
+          const uint32_t p = rk[j] >> kWinPosBits, pos = rk[j] & kPosMask;
+          if (rk[j] != kInvalid && pos / kPkSeg == rnd) win[p * kWinSlots + pos % kPkSeg] = pair_of(j);
+        }
+      } else {  // some slice has closed: the pairs still waiting for one of those leave for the overflow list
+#pragma unroll
+        for (int j = 0; j < kPkRounds; ++j) {
+          const uint32_t p = rk[j] >> kWinPosBits, pos = rk[j] & kPosMask;
+          const bool v = rk[j] != kInvalid && pos / kPkSeg >= rnd;  // (earlier rounds' are written)
+          const bool cl = v && (fill[p] & kWinClosed);
+          const uint2 e = pair_of(j);
+          const bool now = v && !cl && pos / kPkSeg == rnd;
+          if (now) win[p * kWinSlots + pos % kPkSeg] = e;
+          to_ovf(e, p, cl);
+          if (cl || now) rk[j] = kInvalid;
+        }
+      }
+      if (!again) break;
+      __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < kPkRounds; ++j) {
+      ha[j] = hn[j];
+      if constexpr (!IMPLICIT) wa[j] = wn[j];
+      if constexpr (SEL) pa[j] = pn[j];
+    }
+  }
+  // the windows' leftovers: the regions' partial tails (a full region's go to the overflow list)
+  __syncthreads();
+  {
+    const uint32_t f = fill[me], left = (f & kWinClosed) ? 0u : f;  // 0 for threads without a slice
+#pragma unroll
+    for (int j = 0; j < int(kPkSeg) - 1; ++j) {
+      const bool v = uint32_t(j) < left;
+      const uint2 e = v ? win[me * kWinSlots + j] : make_uint2(0, 0);
+      const uint32_t o = my_cur + j;
+      if (v && o < cap) region[my_reg + o] = e;
+      to_ovf(e, me, v && o >= cap);
+    }
+    if (me < P) counts[blockIdx.x * P + me] = min(my_cur + left, cap);
+  }
+  // n_probe: every scanned tuple (the reference's probe count), or the selection's passing tuples
+  if constexpr (SEL) {
+    uint32_t c = npassed;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, kWave);
+    if (lane == 0 && c) atomicAdd(reinterpret_cast<unsigned long long*>(ctl + kCtlNprobe), (unsigned long long)c);
+  } else {
+    if (blockIdx.x == 0 && me == 0) atomicAdd(reinterpret_cast<unsigned long long*>(ctl + kCtlNprobe), (unsigned long long)n);
+  }
+}
+
+template <bool IMPLICIT, bool SEL, int PPT>
+__global__ __launch_bounds__(kPkBlock) void k_pk_part(RelView r, PkGeom pk, uint32_t ntiles, uint32_t cap,
+                                                      uint2* __restrict__ region, uint32_t* __restrict__ counts,
+                                                      uint2* __restrict__ ovf, uint64_t* __restrict__ ctl,
+                                                      SelRange sel, uint32_t stage_lim) {
+  if constexpr (PPT == 1) pk_part_windows<IMPLICIT, SEL>(r, pk, ntiles, cap, region, counts, ovf, ctl, sel);
+  else pk_part_stage<IMPLICIT, SEL, PPT>(r, pk, ntiles, cap, region, counts, ovf, ctl, sel, stage_lim);
 }
 
 // ---- k_pk_split: the second partition level (more than 1024 slices) ----
@@ -1205,18 +1419,18 @@ hipError_t pk_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, uint3
     return e;
   const RelView v = view_of(r);
   const bool imp = r.row_off == HJ3D_ROW_IMPLICIT;
-  const uint32_t slim = ctx->pk_stage ? (ctx->pk_stage < kPkStage ? ctx->pk_stage : kPkStage) : kPkStage;
   {
     KernelSpan tm(ctx, HJ3D_T_SCATTER);
     const uint32_t c32 = uint32_t(L.cap);
-    // (one level beyond 1024 slices: two slices per partitioning thread)
-    const uint32_t slim2 = slim < kPkStage2 ? slim : kPkStage2;
+    // one level beyond 1024 slices: two slices per partitioning thread, the stage form and its
+    // carry-flush threshold (HJ3D_OPT_PK_STAGE); up to 1024 the window form, which has none
+    const uint32_t slim2 = ctx->pk_stage && ctx->pk_stage < kPkStage2 ? ctx->pk_stage : kPkStage2;
 #define HJ3D_PKP_LAUNCH(IMP, SEL)                                                                                   \
   if (pl.P1 > uint32_t(kPkBlock))                                                                                   \
     tm.launch(k_pk_part<IMP, SEL, 2>, dim3(L.G), dim3(kPkBlock), s, v, L.pk1, L.ntiles, c32, L.region, L.counts, L.ovf, L.ctl, sr, \
               slim2);                                                                                               \
   else                                                                                                              \
-    tm.launch(k_pk_part<IMP, SEL, 1>, dim3(L.G), dim3(kPkBlock), s, v, L.pk1, L.ntiles, c32, L.region, L.counts, L.ovf, L.ctl, sr, slim);
+    tm.launch(k_pk_part<IMP, SEL, 1>, dim3(L.G), dim3(kPkBlock), s, v, L.pk1, L.ntiles, c32, L.region, L.counts, L.ovf, L.ctl, sr, 0u);
     if (sel) {
       if (imp) HJ3D_PKP_LAUNCH(true, true)
       else HJ3D_PKP_LAUNCH(false, true)
@@ -1294,10 +1508,10 @@ hipError_t pk_slices(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, uint
   SelRange sr{};
   if (r.row_off == HJ3D_ROW_IMPLICIT)
     hipLaunchKernelGGL((k_pk_part<true, false, 1>), dim3(L.G), dim3(kPkBlock), 0, s, v, L.pk1, L.ntiles, uint32_t(L.cap),
-                       L.region, L.counts, L.ovf, L.ctl, sr, kPkStage);
+                       L.region, L.counts, L.ovf, L.ctl, sr, 0u);
   else
     hipLaunchKernelGGL((k_pk_part<false, false, 1>), dim3(L.G), dim3(kPkBlock), 0, s, v, L.pk1, L.ntiles, uint32_t(L.cap),
-                       L.region, L.counts, L.ovf, L.ctl, sr, kPkStage);
+                       L.region, L.counts, L.ovf, L.ctl, sr, 0u);
   // (C = 1: the split only regroups each slice's G regions into S2)
   hipLaunchKernelGGL(k_pk_split, dim3(L.pk1.P * L.S2), dim3(kSpBlock), 0, s, static_cast<const uint2*>(L.region),
                      static_cast<const uint32_t*>(L.counts), L.G, L.pk1.P, uint32_t(L.cap), L.S2, L.pk, C, bits(C - 1),

@@ -191,9 +191,10 @@ enum {
    * bound puts small tables on that path (tests). It bounds the partitioned nested probe's slice
    * width too: beyond 2048 slices that probe takes the same two-level partition. */
   HJ3D_OPT_PK_SLICE = 8,
-  /* HJ3D_OPT_PK_STAGE (pairs, default 0 = the whole LDS stage): the packed partitioner writes its
-   * carried partial segments out early once the carries plus a tile exceed this many pairs
-   * (tests: 1 flushes after every tile). */
+  /* HJ3D_OPT_PK_STAGE (pairs, default 0 = the whole LDS stage): the packed partitioner's stage form
+   * (two slices per thread: more than 1024 slices in one partition level) writes its carried partial
+   * segments out early once the carries plus a tile exceed this many pairs (tests: 1 flushes after
+   * every tile). The window form (up to 1024 slices) carries nothing and ignores it. */
   HJ3D_OPT_PK_STAGE = 9,
   /* HJ3D_OPT_PK_BUILD (0/1, default 0): chaining builds take the slice build of tables beyond the
    * radix build's range (R through the packed partitioner's two levels into 8192-bucket slices,
