@@ -14,7 +14,9 @@
 //   k_pk_probe  one 1024-thread workgroup per slice (or share of its regions): stages the slice
 //               (directory + entries, entry hashes turned into quotients) in LDS, reserves its
 //               output range with one atomic, probes every pair against LDS in the reference's
-//               walk order with the unique early exit, writes {row, partner} densely; then the
+//               walk order with the unique early exit (K pairs per lane and chunk; the entry reads
+//               of walk positions 0, 1, 2 go out as one batch of 8-B LDS reads per position, no
+//               branch around any of them), writes {row, partner} densely; then the
 //               pairs that overflowed a region (skewed probe keys) are taken in chunks by whichever
 //               workgroups finish first, against the table in HBM; the last workgroup to finish
 //               folds every workgroup's counters into the result slot and resets the control words.
@@ -665,24 +667,28 @@ __device__ __forceinline__ uint64_t pair_ld(const uint2* p) {
 // K = pairs per lane and chunk (the next chunk in flight), chosen per probe from the expected
 // region length (pk_items): a region of L pairs costs ceil(L / 64K) chunks of 64K item slots, so
 // K = 7 walks config B's ~384-pair regions in one 448-slot chunk where K = 8 spends 512 slots.
-// All K items of a chunk have their LDS lookups batched.
+// The LDS lookups of a chunk's items are batched (all K, or two halves of them).
 constexpr int kItemsMin = 5, kItemsMax = 8;
 
 // Unique probe of one lane's items against the LDS slice: directory word (start << 16 | count),
 // entries {q, row} sorted by row inside buckets of <= 32. Walk position c = 0, 1, 2 (sorted index
-// 0, n-1, n-2) batched over K items, the rest per item.
+// 0, n-1, n-2) batched over the items of a group, the rest per item (one merged loop over the
+// later positions of all items measured slower).
 template <int K, int MODE, bool CK>
 __device__ __forceinline__ void pk_probe_items(const uint64_t (&v)[K], uint32_t valid, uint64_t slot0,
                                                const uint32_t* ldir, const uint2* lent, const PkGeom& pk,
                                                uint64_t (&acc)[kProbeFields], uint2* __restrict__ out,
                                                uint64_t out_cap) {
   uint32_t nm = 0, sc = 0, nv = 0;
+  // items per group: the forms whose registers would not hold a whole chunk's lookups (K = 8, and
+  // K = 7 with the checksums) take the chunk in two halves
+  constexpr int H = (K == 8 || (CK && K == 7)) ? (K + 1) / 2 : K;
 #pragma unroll
-  for (int g = 0; g < K; g += K) {
-    uint32_t d[K], match[K], cmps[K], q[K];
-    bool live[K];
+  for (int g = 0; g < K; g += H) {
+    uint32_t d[H], match[H], cmps[H], q[H];
+    bool live[H];
 #pragma unroll
-    for (int j = 0; j < K; ++j) {
+    for (int j = 0; j < H && g + j < K; ++j) {
       const bool ok = (valid >> (g + j)) & 1u;
       const uint32_t x = uint32_t(v[g + j]);
       q[j] = x & pk.qmask;
@@ -694,19 +700,30 @@ __device__ __forceinline__ void pk_probe_items(const uint64_t (&v)[K], uint32_t 
     }
 #pragma unroll
     for (uint32_t c = 0; c < 3; ++c) {
+      // the group's entries of this walk position as one 8-B LDS read each, all issued before the
+      // first compare and waited for with counted waits. The values are pinned as whole 64-bit
+      // registers: left alone, the compiler splits each read into two words and sinks one into a
+      // branch per item with a full wait inside (K serial LDS round trips per position).
+      uint64_t e[H];
+      bool ok[H];
 #pragma unroll
-      for (int j = 0; j < K; ++j) {
+      for (int j = 0; j < H && g + j < K; ++j) {
         const uint32_t nn = d[j] & 0xFFFFu;
-        const bool ok = live[j] && c < nn;
-        const uint2 e = lent[ok ? (d[j] >> 16) + (c == 0 ? 0u : nn - c) : 0u];
-        const bool hit = ok && e.x == q[j];
-        match[j] = hit ? e.y : match[j];
+        ok[j] = live[j] && c < nn;
+        e[j] = *reinterpret_cast<const uint64_t*>(lent + (ok[j] ? (d[j] >> 16) + (c == 0 ? 0u : nn - c) : 0u));
+      }
+#pragma unroll
+      for (int j = 0; j < H && g + j < K; ++j) asm volatile("" : "+v"(e[j]));
+#pragma unroll
+      for (int j = 0; j < H && g + j < K; ++j) {
+        const bool hit = ok[j] && uint32_t(e[j]) == q[j];
+        match[j] = hit ? uint32_t(e[j] >> 32) : match[j];
         cmps[j] = hit ? c + 1 : cmps[j];
         live[j] = live[j] && !hit;
       }
     }
 #pragma unroll
-    for (int j = 0; j < K; ++j) {
+    for (int j = 0; j < H && g + j < K; ++j) {
       const uint32_t nn = d[j] & 0xFFFFu, s = d[j] >> 16;
       if (live[j] && nn > 3) {
         for (uint32_t c = 3; c < nn; ++c) {
@@ -740,7 +757,7 @@ __device__ __forceinline__ void pk_probe_items(const uint64_t (&v)[K], uint32_t 
       }
     }
 #pragma unroll
-    for (int j = 0; j < K; ++j) {
+    for (int j = 0; j < H && g + j < K; ++j) {
       const bool ok = (valid >> (g + j)) & 1u;
       const uint32_t row = uint32_t(v[g + j] >> 32);
       const bool m = match[j] != kInvalid;
