@@ -355,6 +355,7 @@ void hj3d_ctx_destroy(hj3d_ctx* ctx) {
   for (auto& b : ctx->scratch) b.release();
   ctx->res.release();
   ctx->resn.release();
+  ctx->resa.release();
   ctx->misc.release();
   ctx->ctl.release();
   ctx->scan_status.release();
@@ -1021,6 +1022,87 @@ hj3d_status hj3d_select_nested(hj3d_ctx* ctx, const void* nested_dev, uint64_t n
   if (e == hipSuccess) e = out_check(ctx, false, flags, out_cap);
   note_probe(ctx, false, flags, n, out_cap);
   return from_hip(ctx, e, me);
+}
+
+hj3d_status hj3d_group_agg(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* build, uint32_t word_off,
+                           uint32_t is_signed, void* out_dev, uint64_t out_cap) {
+  const char* const me = "hj3d_group_agg";
+  if (!ctx || !t || !build) return HJ3D_EINVAL;
+  if (t->desc.kind != HJ3D_NESTED) return fail_in(ctx, me, "needs a nested table");
+  if (!rel_ok(build) || build->row_off != HJ3D_ROW_IMPLICIT)
+    return fail_in(ctx, me, "invalid build relation (implicit rows only)");
+  if ((word_off & 3) || uint64_t(word_off) + 4 > build->stride) return fail_in(ctx, me, "word_off outside the tuple");
+  if (uintptr_t(out_dev) & 7) return fail_in(ctx, me, "misaligned output buffer");
+  if (hipError_t re = resolve(ctx, t); re != hipSuccess) return from_hip(ctx, re, me);
+  if (t->n_mains && !out_dev) return fail_in(ctx, me, "no output buffer");
+  if (out_cap < t->n_mains) return fail(ctx, HJ3D_EOVERFLOW, "hj3d_group_agg: fewer output records than main records");
+  PhaseTimer tm(ctx, HJ3D_T_PROBE);
+  const hipError_t e = group_agg(ctx, t, *build, word_off, is_signed != 0, out_dev, ctx->res.as<uint64_t>(), ctx->stream);
+  note_probe(ctx, true, 0, t->n_mains, out_cap);
+  return from_hip(ctx, e, me);
+}
+
+hj3d_status hj3d_agg_nested(hj3d_ctx* ctx, const void* nested_dev, uint64_t n, uint32_t k,
+                            const hj3d_table* const* tables, const hj3d_agg_spec* specs, uint32_t nspec, uint32_t flags,
+                            void* out_dev, uint64_t out_cap) {
+  const char* const me = "hj3d_agg_nested";
+  if (!ctx || !tables) return HJ3D_EINVAL;
+  if (k < 1 || k > HJ3D_NEST_MAX) return fail_in(ctx, me, "k must be 1 .. HJ3D_NEST_MAX");
+  for (uint32_t i = 0; i < k; ++i)
+    if (!tables[i]) return fail_in(ctx, me, "a null table");
+  if (nspec < 1 || nspec > HJ3D_AGG_MAX || !specs) return fail_in(ctx, me, "nspec must be 1 .. HJ3D_AGG_MAX");
+  if (flags & ~HJ3D_PROBE_EMIT) return fail_in(ctx, me, "flags other than EMIT");
+  for (uint32_t i = 0; i < k; ++i)
+    if (tables[i]->desc.kind != HJ3D_NESTED) return fail_in(ctx, me, "needs nested tables");
+  if ((n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32)) return fail_in(ctx, me, "invalid input");
+  if (uintptr_t(out_dev) & 7) return fail_in(ctx, me, "misaligned output buffer");
+  if (const hj3d_status st = emit_buffer_ok(ctx, me, flags, out_dev, out_cap); st != HJ3D_OK) return st;
+  for (uint32_t q = 0; q < nspec; ++q) {
+    const hj3d_agg_spec& sp = specs[q];
+    if (sp.op > HJ3D_AGG_MAX_) return fail_in(ctx, me, "unknown aggregate");
+    if (sp.op == HJ3D_AGG_COUNT ? sp.slot != 0 : (sp.slot < 1 || sp.slot > k))
+      return fail_in(ctx, me, "a spec's slot outside 1 .. k (COUNT: not 0)");
+    if (sp.op != HJ3D_AGG_COUNT && (!sp.gcol || (uintptr_t(sp.gcol) & 7))) return fail_in(ctx, me, "a spec without its column");
+  }
+  for (uint32_t i = 0; i < k; ++i)
+    if (hipError_t re = resolve(ctx, tables[i]); re != hipSuccess) return from_hip(ctx, re, me);
+  for (uint32_t q = 0; q < nspec; ++q)  // (the main-record counts are known once the builds are finished)
+    if (specs[q].op != HJ3D_AGG_COUNT && specs[q].gcol_n < tables[specs[q].slot - 1]->n_mains)
+      return fail_in(ctx, me, "a column shorter than its table's main records");
+  if (hipError_t ae = ctx->resa.ensure(kAggnWords * sizeof(uint64_t)); ae != hipSuccess) return from_hip(ctx, ae, me);
+  PhaseTimer tm(ctx, HJ3D_T_PROBE);
+  const hipError_t e = agg_nested(ctx, nested_dev, n, k, tables, specs, nspec, flags, out_dev, out_cap,
+                                  ctx->resa.as<uint64_t>(), ctx->stream);
+  ctx->resa_n = n;
+  ctx->resa_cap = (flags & HJ3D_PROBE_EMIT) ? out_cap : ~0ull;
+  ctx->resa_nspec = nspec;
+  for (uint32_t q = 0; q < nspec; ++q) {
+    ctx->resa_op[q] = specs[q].op;
+    ctx->resa_sgn[q] = specs[q].is_signed != 0;
+  }
+  return from_hip(ctx, e, me);
+}
+
+hj3d_status hj3d_agg_nested_result(hj3d_ctx* ctx, hj3d_aggn_res* out) {
+  if (!ctx || !out) return HJ3D_EINVAL;
+  std::memset(out, 0, sizeof(*out));
+  if (!ctx->resa.p) return fail(ctx, HJ3D_EINVAL, "hj3d_agg_nested_result: no hj3d_agg_nested before it");
+  uint64_t h[kAggnWords];
+  if (const hj3d_status st = read_slot(ctx, "hj3d_agg_nested_result", ctx->resa.p, h, kAggnWords); st != HJ3D_OK) return st;
+  out->n_in = ctx->resa_n;
+  out->n_live = h[0];
+  // the magnitude rule of hj3d_unnestn
+  if (h[kAggnFlag] != 0 || h[kAggnHi] + (h[kAggnLo] >> 32) >= (1ull << 31))
+    return fail(ctx, HJ3D_EUNSUPPORTED, "hj3d_agg_nested: a tuple's product or c_top reaches 2^63");
+  out->c_top = h[kAggnCTop];
+  for (uint32_t q = 0; q < HJ3D_AGG_MAX; ++q) {
+    const uint32_t op = q < ctx->resa_nspec ? ctx->resa_op[q] : uint32_t(HJ3D_AGG_COUNT);
+    const bool mm = op == HJ3D_AGG_MIN || op == HJ3D_AGG_MAX_;
+    out->total[q] = q < ctx->resa_nspec ? agg_total_decode(h[(mm ? kAggnMm : kAggnAdd) + q], op, ctx->resa_sgn[q]) : 0;
+  }
+  // every input tuple has a row; those past the buffer were not written
+  if (ctx->resa_n > ctx->resa_cap) return fail(ctx, HJ3D_EOVERFLOW, "hj3d_agg_nested: output buffer too small");
+  return HJ3D_OK;
 }
 
 hj3d_status hj3d_probe_geometry(hj3d_ctx* ctx, uint64_t nb_local, uint64_t n_build, uint32_t out[5]) {

@@ -36,6 +36,10 @@ constexpr uint32_t kRefGroup = 8;     // hj3d_probe_ref / hj3d_probe_refn: tuple
 // reached 2^63), then sum_a, sum_row[HJ3D_NEST_MAX], sum_h, xor_h (unnestn.hip)
 constexpr int kUnnCTop = 1 + HJ3D_NEST_MAX, kUnnHi = kUnnCTop + 1, kUnnLo = kUnnHi + 1, kUnnFlag = kUnnLo + 1;
 constexpr int kUnnSumA = kUnnFlag + 1, kUnnWords = kUnnSumA + 3 + HJ3D_NEST_MAX;
+// hj3d_agg_nested's device result slot (u64 words): n_live, c_top, the magnitude words as above, then
+// the COUNT / SUM totals and the MIN / MAX totals (as keys), HJ3D_AGG_MAX words each (agg_nested.hip)
+constexpr int kAggnCTop = 1, kAggnHi = 2, kAggnLo = 3, kAggnFlag = 4, kAggnAdd = 5, kAggnMm = kAggnAdd + HJ3D_AGG_MAX;
+constexpr int kAggnWords = kAggnMm + HJ3D_AGG_MAX;
 
 // Grow-only device buffer (allocation happens outside timed loops once sizes are warm).
 struct DevBuf {
@@ -152,6 +156,11 @@ struct hj3d_ctx {
   hj3d::DevBuf resn;
   uint64_t resn_n = 0, resn_cap = ~0ull;
   uint32_t resn_flags = 0;
+  // hj3d_agg_nested: its own result slot (kAggnWords words), the input tuples, output capacity and
+  // specs (op, signedness) of the last call (hj3d_agg_nested_result)
+  hj3d::DevBuf resa;
+  uint64_t resa_n = 0, resa_cap = ~0ull;
+  uint32_t resa_nspec = 0, resa_op[HJ3D_AGG_MAX] = {0}, resa_sgn[HJ3D_AGG_MAX] = {0};
   hipError_t ensure_ctl() {
     if (ctl.p) return hipSuccess;
     hipError_t e = ctl.ensure(128 * sizeof(uint64_t));  // 8 control words; [64, 128): store sink
@@ -480,6 +489,17 @@ hipError_t select_nested(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t k, 
                          const hj3d_table* const* tables, const hj3d_rel* builds, const hj3d_nsel_pred* preds,
                          uint32_t npred, uint32_t flags, void* out, uint64_t out_cap, uint64_t* res_dev,
                          hipStream_t s);
+// group_agg.hip: hj3d_group_agg, {sum, min, max} of the u32 at word_off of `build` over every group of the
+// nested table t (resolved, validated arguments), one hj3d_gagg per main record into out; res: the probe
+// result slot, cleared here. Uses scratch kScrA (hot-group list) and kScrB (its skip words).
+hipError_t group_agg(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& build, uint32_t word_off, bool is_signed,
+                     void* out, uint64_t* res_dev, hipStream_t s);
+// agg_nested.hip: hj3d_agg_nested, n tuples {a, ref_1 .. ref_k} of tables[0 .. k) aggregated by nspec specs
+// (res: the kAggnWords words of ctx->resa, cleared here); agg_total_decode: a total's value from its word
+hipError_t agg_nested(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t k, const hj3d_table* const* tables,
+                      const hj3d_agg_spec* specs, uint32_t nspec, uint32_t flags, void* out, uint64_t out_cap,
+                      uint64_t* res_dev, hipStream_t s);
+uint64_t agg_total_decode(uint64_t word, uint32_t op, uint32_t is_signed);
 // exp4.hip
 hipError_t probe2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const hj3d_rel& r, uint32_t flags,
                   void* out, uint64_t out_cap, uint64_t* res_dev, hipStream_t s);

@@ -36,6 +36,9 @@ OPT_DIAG_LOOKBACK = 17
 SEL_LT, SEL_LE, SEL_GT, SEL_GE, SEL_EQ, SEL_NE, SEL_RANGE = range(7)
 SEL_MAX = 4
 NSEL_BASE, NSEL_COUNT, NSEL_FIRST = range(3)  # where a nested-tuple predicate takes its u32 (select_nested)
+AGG_MAX = 8  # aggregates one agg_nested call computes (HJ3D_AGG_MAX)
+AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX_ = range(4)
+AGG_OPS = {"count": AGG_COUNT, "sum": AGG_SUM, "min": AGG_MIN, "max": AGG_MAX_}
 SEL_OPS = {"<": SEL_LT, "<=": SEL_LE, ">": SEL_GT, ">=": SEL_GE, "==": SEL_EQ, "!=": SEL_NE, "range": SEL_RANGE}
 
 MASK64 = (1 << 64) - 1
@@ -81,6 +84,15 @@ class _SelPred(C.Structure):
 
 class _NSelPred(C.Structure):
     _fields_ = [("source", C.c_uint32), ("slot", C.c_uint32), ("pred", _SelPred)]
+
+
+class _AggSpec(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("slot", C.c_uint32), ("is_signed", C.c_uint32), ("reserved", C.c_uint32),
+                ("gcol", C.c_void_p), ("gcol_n", C.c_uint64)]
+
+
+class _AggNRes(C.Structure):
+    _fields_ = [("n_in", C.c_uint64), ("n_live", C.c_uint64), ("c_top", C.c_uint64), ("total", C.c_uint64 * AGG_MAX)]
 
 
 class _Stats(C.Structure):
@@ -163,6 +175,9 @@ def lib():
         "hj3d_select": (st, [p, R, C.POINTER(_SelPred), u32, p, p]),
         "hj3d_probe_sel": (st, [p, p, R, C.POINTER(_SelPred), u32, u32, p, u64]),
         "hj3d_select_nested": (st, [p, p, u64, u32, R, C.POINTER(p), R, C.POINTER(_NSelPred), u32, u32, p, u64]),
+        "hj3d_group_agg": (st, [p, p, R, u32, u32, p, u64]),
+        "hj3d_agg_nested": (st, [p, p, u64, u32, C.POINTER(p), C.POINTER(_AggSpec), u32, u32, p, u64]),
+        "hj3d_agg_nested_result": (st, [p, C.POINTER(_AggNRes)]),
         "hj3d_gen_keys": (st, [p, p, u64, u32, u32, u64, u64, u64]),
         "hj3d_gen_fk": (st, [p, p, u64, u32, u32, u64, u32, u64]),
         "hj3d_gen_zipf": (st, [p, p, u64, u32, u32, u64, u32, C.c_double, u64]),
@@ -610,6 +625,58 @@ class Context:
                                              _nsel_preds(preds), len(preds), flags, ptr, cap), "hj3d_select_nested")
         return self.probe_result() if fetch else None
 
+    # ---- aggregation over stored nested tuples without unnesting ----
+    def agg_nested(self, nested, tables, specs, out=None, fetch: bool = True) -> Optional[dict]:
+        """hj3d_agg_nested: aggregates over the rows the tuples {a, ref_1 .. ref_k} of `nested` (a contiguous
+        (n, k + 1) int32 device tensor; ref_i a main ref of tables[i - 1], k = len(tables)) would unnest to.
+        specs: ("count",) or ("sum" | "min" | "max", slot, column[, signed]) with slot 1..k and column
+        the (n_mains, 3) int64 device tensor Table.group_agg returned for tables[slot - 1] (signed, default
+        True: as that column was built). out: a contiguous (cap, len(specs)) int64 device tensor that
+        receives one row of values per input tuple, in input order (None: totals only). The result is
+        agg_nested_result()'s dict."""
+        torch = _torch()
+        k = len(tables)
+        if not 1 <= k <= HJ3D_NEST_MAX:
+            raise ValueError(f"agg_nested takes 1..{HJ3D_NEST_MAX} tables")
+        if not 1 <= len(specs) <= AGG_MAX:
+            raise ValueError(f"agg_nested takes 1..{AGG_MAX} specs")
+        ptr_in, n = _words(nested, k + 1, "nested")
+        arr = (_AggSpec * len(specs))()
+        for i, sp in enumerate(specs):
+            if sp[0] not in AGG_OPS:
+                raise ValueError(f"unknown aggregate {sp[0]!r} (count, sum, min, max)")
+            if sp[0] == "count":
+                arr[i] = _AggSpec(AGG_COUNT, 0, 0, 0, None, 0)
+                continue
+            col = sp[2]
+            if not col.is_cuda or col.dtype != torch.int64 or col.dim() != 2 or col.shape[1] != 3 or not col.is_contiguous():
+                raise ValueError("a spec's column must be a contiguous (n_mains, 3) int64 device tensor")
+            signed = sp[3] if len(sp) > 3 else True
+            arr[i] = _AggSpec(AGG_OPS[sp[0]], int(sp[1]), int(bool(signed)), 0, col.data_ptr() if col.shape[0] else None,
+                              col.shape[0])
+        emit, ptr, cap = 0, None, 0
+        if out is not None:
+            if not out.is_cuda or out.dtype != torch.int64 or out.dim() != 2 or out.shape[1] != len(specs) or \
+                    not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous (cap, {len(specs)}) int64 device tensor")
+            emit, ptr, cap = PROBE_EMIT, (out.data_ptr() if out.shape[0] else None), out.shape[0]
+        th = (C.c_void_p * k)(*[t.h for t in tables])
+        self._check(lib().hj3d_agg_nested(self.h, ptr_in, n, k, th, arr, len(specs), emit, ptr, cap), "hj3d_agg_nested")
+        self._aggn_nspec = len(specs)
+        return self.agg_nested_result() if fetch else None
+
+    def agg_nested_result(self) -> dict:
+        """The last agg_nested's result: n_in, n_live, c_top (= unnestn's), total (one per spec: the sum
+        mod 2^64 of COUNT / SUM values, the min / max over the live tuples as a 64-bit two's complement
+        word), overflow (fewer output rows than tuples). Raises Hj3dError(HJ3D_EUNSUPPORTED) when a
+        tuple's product or c_top reaches 2^63."""
+        r = _AggNRes()
+        st = lib().hj3d_agg_nested_result(self.h, C.byref(r))
+        if st not in (HJ3D_OK, HJ3D_EOVERFLOW):
+            self._check(st, "hj3d_agg_nested_result")
+        return {"n_in": r.n_in, "n_live": r.n_live, "c_top": r.c_top,
+                "total": list(r.total)[:getattr(self, "_aggn_nspec", AGG_MAX)], "overflow": st == HJ3D_EOVERFLOW}
+
     def packed_probe(self, on: bool = True):
         """A/B switch: the unique chaining probe on packed pairs (default) or on (hash, row) pairs."""
         self.set_option(OPT_PACKED_PROBE, int(on))
@@ -1002,6 +1069,29 @@ class Table:
                         "hj3d_table_export")
         return off, payload, sub
 
+    def group_agg(self, rel: Rel, word: int, signed: bool = True, out=None, fetch: bool = True):
+        """hj3d_group_agg: {sum, min, max} of word `word` of `rel` (the relation the table was built from,
+        implicit rows) over every group, read as int32 (signed) or uint32 and extended to 64 bits. Returns
+        (column, result): the (n_mains, 3) int64 device tensor indexed by main ref (a view of `out`, a
+        contiguous (cap, 3) int64 device tensor, when given, and `out` itself with fetch=False, which
+        reads nothing back; Hj3dError(HJ3D_EOVERFLOW) when cap is below the main-record count), and the
+        ProbeResult (n_probe = main records, n_matched = groups folded
+        whole, n_out = rows folded, sum_a = the sum of the sums) or None with fetch=False. The column
+        feeds Context.agg_nested and is valid until the table's next build or clear."""
+        torch = _torch()
+        n_mains = None
+        if out is None:  # (the main-record count is read from the table: synchronous)
+            n_mains = self.size()[1] if self.kind == HJ3D_NESTED else 0
+            out = torch.empty((n_mains, 3), dtype=torch.int64, device=f"cuda:{self.ctx.device}")
+        elif not out.is_cuda or out.dtype != torch.int64 or out.dim() != 2 or out.shape[1] != 3 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous (cap, 3) int64 device tensor")
+        self.ctx._check(lib().hj3d_group_agg(self.ctx.h, self.h, C.byref(rel.c), 4 * word, int(bool(signed)),
+                                             out.data_ptr() if out.shape[0] else None, out.shape[0]), "hj3d_group_agg")
+        r = self.ctx.probe_result() if fetch else None
+        if r is not None:
+            n_mains = r.n_probe
+        return (out if n_mains is None else out[:n_mains]), r
+
     def close(self):
         if getattr(self, "h", None):
             lib().hj3d_table_destroy(self.h)
@@ -1016,4 +1106,4 @@ class Table:
 
 from .plans import (EXP1_PLANS, exp1_plan, exp1_plan_sharded, exp1_relations_ref, exp4_plan,  # noqa: E402,F401
                     exp4_plan_chained, exp4_plan_sharded, exp4_relations_ref, merge_exp4, merge_shard_stats, num_buckets_exp1,
-                    num_distinct_sharded, star_plan_chained)
+                    num_distinct_sharded, star_plan_aggregate, star_plan_chained)

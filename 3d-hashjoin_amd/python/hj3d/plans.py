@@ -267,19 +267,10 @@ def exp4_plan_chained(ctx: Context, R, S, T, nb, keys=(0, 0), out=None, checksum
     return res
 
 
-def star_plan_chained(ctx: Context, R, builds, nb, keys, out=None, checksum: bool = True, filters=None) -> dict:
-    """A k-way star Ndu from the separate operators, AlgNestJoinProbe / AlgUnnestHt stacked k deep
-    (algebra.hh:435-541; experiment 4 is k = 2): one nested table per (relation, key word) in `builds`
-    (an entry given twice shares its table: a self join), then probe(mainref) on R.keys[0], probe_refn
-    on each further R.keys[i] (its input is the previous level's survivors), then unnestn over the k
-    tables, all on the device. nb: the bucket count of every table, or one per build; keys: the R word
-    of each join attribute; out: a (cap, k + 1) int32 device tensor for the output rows
-    {r_row, row_1 .. row_k}. Returns Context.unnestn_result()'s dict plus the per-level lists
-    c_probe (tuples with a match) and c_probe_cmp (collision-chain comparisons).
-    filters: {level: preds}, a selection (AlgSelection, algebra.hh:278-358) stacked on level i's probe
-    (0-based): Context.select_nested over that level's output, with R as base and the tables and build
-    relations so far; the next level (or the unnest) sees only the passing tuples. The result then
-    gains c_select, the passing tuples per level (None where a level has no filter)."""
+def _star_chain(ctx: Context, R, builds, nb, keys, filters):
+    """The chain both star plans share: the k nested tables, probe(mainref) on R.keys[0], probe_refn on each
+    further R.keys[i], a select_nested behind every level that has a filter. Returns (tables, the last
+    level's tuples {r_row, ref_1 .. ref_k}, the per-level lists as a dict)."""
     import torch
     k = len(builds)
     if len(keys) != k:
@@ -316,10 +307,53 @@ def star_plan_chained(ctx: Context, R, builds, nb, keys, out=None, checksum: boo
         c_probe.append(r.n_matched)
         c_cmp.append(r.n_cmps)
         cur, live = selected(i, cur, r.n_out)
-    res = ctx.unnestn(tables, cur, out=out, checksum=checksum)
-    res.update(c_probe=c_probe, c_probe_cmp=c_cmp)
+    levels = {"c_probe": c_probe, "c_probe_cmp": c_cmp}
     if filters is not None:
-        res["c_select"] = c_select
+        levels["c_select"] = c_select
+    return tables, cur, levels
+
+
+def star_plan_chained(ctx: Context, R, builds, nb, keys, out=None, checksum: bool = True, filters=None) -> dict:
+    """A k-way star Ndu from the separate operators, AlgNestJoinProbe / AlgUnnestHt stacked k deep
+    (algebra.hh:435-541; experiment 4 is k = 2): one nested table per (relation, key word) in `builds`
+    (an entry given twice shares its table: a self join), then probe(mainref) on R.keys[0], probe_refn
+    on each further R.keys[i] (its input is the previous level's survivors), then unnestn over the k
+    tables, all on the device. nb: the bucket count of every table, or one per build; keys: the R word
+    of each join attribute; out: a (cap, k + 1) int32 device tensor for the output rows
+    {r_row, row_1 .. row_k}. Returns Context.unnestn_result()'s dict plus the per-level lists
+    c_probe (tuples with a match) and c_probe_cmp (collision-chain comparisons).
+    filters: {level: preds}, a selection (AlgSelection, algebra.hh:278-358) stacked on level i's probe
+    (0-based): Context.select_nested over that level's output, with R as base and the tables and build
+    relations so far; the next level (or the unnest) sees only the passing tuples. The result then
+    gains c_select, the passing tuples per level (None where a level has no filter).
+    star_plan_aggregate ends the same chain in aggregates instead of the unnest."""
+    tables, cur, levels = _star_chain(ctx, R, builds, nb, keys, filters)
+    res = ctx.unnestn(tables, cur, out=out, checksum=checksum)
+    res.update(levels)
+    return res
+
+
+def star_plan_aggregate(ctx: Context, R, builds, nb, keys, aggregate, out=None, filters=None) -> dict:
+    """star_plan_chained's chain (same R, builds, nb, keys, filters) ending in aggregates over the join
+    result instead of the result itself, computed without unnesting. aggregate: [("count",), ("sum" | "min"
+    | "max", level, word[, signed]), ..]: Table.group_agg of word `word` of build `level` (0-based, as in
+    filters; once per distinct (level, word, signed)), then Context.agg_nested over the last level's tuples
+    in place of unnestn. Returns Context.agg_nested_result()'s dict (n_in, n_live, c_top, total: one per
+    entry, overflow) plus the per-level lists; out: a (cap, len(aggregate)) int64 device tensor for the
+    per-tuple values, row i those of the i-th tuple that reached the last level."""
+    tables, cur, levels = _star_chain(ctx, R, builds, nb, keys, filters)
+    cols, specs = {}, []
+    for sp in aggregate:
+        if sp[0] == "count":
+            specs.append(("count",))
+            continue
+        level, word, signed = sp[1], sp[2], (sp[3] if len(sp) > 3 else True)
+        if (level, word, signed) not in cols:
+            rel, kw = builds[level]
+            cols[(level, word, signed)] = tables[level].group_agg(Rel(rel, key_word=kw), word, signed, fetch=False)[0]
+        specs.append((sp[0], level + 1, cols[(level, word, signed)], signed))
+    res = ctx.agg_nested(cur, tables, specs, out=out)
+    res.update(levels)
     return res
 
 

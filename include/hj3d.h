@@ -32,6 +32,8 @@
  *   hj3d_select_nested         AlgSelection / AlgDynSelection::step between AlgNestJoinProbe and
  *                              AlgUnnestHt, over stored nested tuples   algebra.hh:278-358 on 435-459,
  *                                                                     main_algebra_example.cc:226-234, 305-316
+ *   hj3d_group_agg,            (no counterpart) aggregates over the rows stored nested tuples would unnest
+ *   hj3d_agg_nested            to, without running AlgUnnestHt::step   algebra.hh:490-541
  *
  * Semantics kept bit-exact with the reference: hash = murmur3 fmix32 (util/hasht.hh:52-61),
  * bucket = hash % num_buckets, and every counter the reference reports (match counts,
@@ -688,6 +690,71 @@ hj3d_status hj3d_select_nested(hj3d_ctx* ctx, const void* nested_dev, uint64_t n
                                const hj3d_rel* base, const hj3d_table* const* tables, const hj3d_rel* builds,
                                const hj3d_nsel_pred* preds, uint32_t npred,
                                uint32_t flags, void* out_dev, uint64_t out_cap);
+
+/* ---- aggregation over stored nested tuples without unnesting ----
+ * The reference has no aggregation operator: a plan that wants COUNT(*), SUM(s.b) or MIN(t.b) per probe
+ * tuple, or over the whole join, runs its unnest functors (AlgUnnestHt::step, algebra.hh:490-541) and
+ * reduces their output. The nested representation already holds what these aggregates need: with G_i the
+ * group ref_i names, the aggregates over the rows a tuple {a, ref_1 .. ref_k} would unnest to are
+ *   COUNT = prod |G_j|,  SUM(builds[i].w) = (sum of w over G_i) * prod_{j != i} |G_j|,
+ *   MIN / MAX(builds[i].w) = min / max of w over G_i,
+ * so no output row is needed. hj3d_group_agg reduces a build word per group (it depends on the table and
+ * the build column only and is reused by any number of probes and plans); hj3d_agg_nested combines. */
+/* One record of hj3d_group_agg's column, indexed by main ref. */
+typedef struct { uint64_t sum, min, max; } hj3d_gagg;
+/* hj3d_group_agg: for every main record m of the nested table t, fold the u32 at word_off of the tuple
+ * row - build->row_base of `build` (implicit rows) over the rows of m's group, sign-extended (is_signed)
+ * or zero-extended to 64 bits: out_dev[m] = {sum, min, max}, sum exact in two's complement (fewer than
+ * 2^32 rows, each below 2^32 in magnitude: no overflow), min / max the extended values (as int64 /
+ * uint64). A row that is not a row of `build` (the caller passed another relation than the one the table
+ * was built from) is skipped and no memory is read through it; a group with no folded row gets the
+ * identities: sum 0, min = INT64_MAX / UINT64_MAX, max = INT64_MIN / 0 (signed / unsigned).
+ * Result (the probe result slot, hj3d_probe_result): n_probe = main records, n_matched = groups all of
+ * whose rows were folded, n_out = rows folded, sum_a = the sum of all sum fields mod 2^64, the rest 0.
+ * HJ3D_EOVERFLOW if out_cap is below the table's main-record count (known on the host once a pending
+ * build is finished, which the call does first, as a probe does); nothing is written then. HJ3D_EINVAL: a
+ * null ctx / t / build, a chaining table, an invalid build relation or one with explicit rows, word_off
+ * not a multiple of 4 or not inside the tuple, out_dev not 8-byte aligned, out_dev == NULL with a
+ * non-empty table. A cleared table writes nothing and reports zeros. The column is valid as long as main
+ * refs are: until the table's next hj3d_build, hj3d_build_many or hj3d_table_clear. Otherwise
+ * asynchronous on the context stream. */
+hj3d_status hj3d_group_agg(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel* build, uint32_t word_off,
+                           uint32_t is_signed, void* out_dev, uint64_t out_cap);
+
+#define HJ3D_AGG_MAX 8 /* aggregates one hj3d_agg_nested call computes */
+enum { HJ3D_AGG_COUNT = 0, HJ3D_AGG_SUM, HJ3D_AGG_MIN, HJ3D_AGG_MAX_ };
+typedef struct {
+  uint32_t op, slot;            /* HJ3D_AGG_*; slot 1..k: the group aggregated; COUNT: 0               */
+  uint32_t is_signed, reserved; /* MIN / MAX compare as int64 or uint64 (as the column was built)      */
+  const void* gcol;             /* hj3d_gagg column of tables[slot - 1] (device, 8-byte aligned); COUNT: NULL */
+  uint64_t gcol_n;              /* its records; must be >= that table's main-record count              */
+} hj3d_agg_spec;
+typedef struct { uint64_t n_in, n_live, c_top; uint64_t total[HJ3D_AGG_MAX]; } hj3d_aggn_res;
+/* hj3d_agg_nested: nested_dev holds n tuples {u32 a, u32 ref_1 .. ref_k} (4-byte aligned), ref_i a main ref
+ * of tables[i - 1], 1 <= k <= HJ3D_NEST_MAX. Liveness is hj3d_unnestn's: a tuple with any ref not below its
+ * table's current main-record count is dead and nothing is read through it. Per tuple and spec, over the
+ * rows the tuple would unnest to, with P = prod |G_j|: COUNT = P; SUM = gcol[ref_slot].sum * (P / |G_slot|),
+ * computed as the product of the other lengths in u64 arithmetic mod 2^64 (the engine's sum_* counters
+ * wrap the same way); MIN / MAX = gcol[ref_slot].min / .max. A dead tuple gives COUNT 0, SUM 0 and MIN / MAX
+ * the identities of hj3d_group_agg.
+ * With HJ3D_PROBE_EMIT row i of out_dev holds the nspec u64 values of input tuple i (dense, input order: a
+ * column aligned with the nested tuples), at most out_cap rows; nothing is written at or beyond
+ * out_dev + 8 nspec out_cap. hj3d_agg_nested_result returns HJ3D_EOVERFLOW (with the complete totals) when
+ * n > out_cap under EMIT. total[s] = the sum mod 2^64 of spec s's values (COUNT, SUM), or their min / max
+ * over the live tuples (the identity if there are none); c_top = the sum of P = hj3d_unnestn's c_top.
+ * The magnitude rule is hj3d_unnestn's: a tuple's P, or c_top, at or beyond 2^63 makes
+ * hj3d_agg_nested_result return HJ3D_EUNSUPPORTED with only n_in and n_live set.
+ * flags: HJ3D_PROBE_EMIT only. HJ3D_EINVAL: any other flag, a null ctx / tables / entry of tables, a chaining
+ * table, k outside 1 .. HJ3D_NEST_MAX, nspec outside 1 .. HJ3D_AGG_MAX (or a null specs), an unknown op, a
+ * slot outside 1 .. k (COUNT: not 0), a null gcol where one is needed, gcol_n below the table's main-record
+ * count, nested_dev not 4-byte or out_dev / gcol not 8-byte aligned, n && !nested_dev, EMIT with
+ * out_dev == NULL and out_cap > 0, n >= 2^32; hj3d_agg_nested_result before any hj3d_agg_nested. The result
+ * has a slot of its own: the probe and hj3d_unnestn result slots are not touched. Asynchronous; pending
+ * nested builds of the given tables are finished first, as by a probe. */
+hj3d_status hj3d_agg_nested(hj3d_ctx* ctx, const void* nested_dev, uint64_t n, uint32_t k,
+                            const hj3d_table* const* tables, const hj3d_agg_spec* specs, uint32_t nspec,
+                            uint32_t flags, void* out_dev, uint64_t out_cap);
+hj3d_status hj3d_agg_nested_result(hj3d_ctx* ctx, hj3d_aggn_res* out);
 
 /* ---- synthetic key/FK relations generated on the device (bench / full-size checks) ----
  * R.k = a seeded bijective permutation of [0, n_keys) (keys for global rows
