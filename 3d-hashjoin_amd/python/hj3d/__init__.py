@@ -374,6 +374,24 @@ class Context:
     def sync(self):
         self._check(lib().hj3d_ctx_sync(self.h), "sync")
 
+    def set_stream(self, stream):
+        """hj3d_ctx_set_stream: later calls are enqueued on `stream` (a torch.cuda.Stream). Nothing orders
+        the new stream after the old one: the caller does (stream.wait_stream(old), an event, a sync)
+        before work on the new stream reads what calls on the old one wrote."""
+        self._check(lib().hj3d_ctx_set_stream(self.h, C.c_void_p(stream.cuda_stream)), "hj3d_ctx_set_stream")
+        self.stream = stream
+
+    def stream_handle(self) -> int:
+        """The HIP stream handle the library enqueues on (hj3d_ctx_stream); 0 = the null stream."""
+        return lib().hj3d_ctx_stream(self.h) or 0
+
+    def on_stream(self):
+        """torch's current stream = the context's, for the block. Every device tensor a wrapper allocates
+        or fills itself (counters it zeroes, outputs it sizes) is made under it: the library writes them
+        on the context's stream, and a fill on another stream would be a second, unordered writer (and
+        the caching allocator would hand the block out for a stream that does not use it)."""
+        return _torch().cuda.stream(self.stream)
+
     def set_option(self, option: int, value: int):
         self._check(lib().hj3d_ctx_set_option(self.h, option, value), "set_option")
 
@@ -565,10 +583,11 @@ class Context:
             raise ValueError(f"at most {SEL_MAX} predicates")
         arr = _sel_preds(preds)
         dev = f"cuda:{self.device}"
-        if out_pairs is None:
-            out_pairs = torch.empty((max(rel.n, 1), 2), dtype=torch.int32, device=dev)
-        if count is None:
-            count = torch.zeros(1, dtype=torch.int64, device=dev)
+        with self.on_stream():
+            if out_pairs is None:
+                out_pairs = torch.empty((max(rel.n, 1), 2), dtype=torch.int32, device=dev)
+            if count is None:
+                count = torch.zeros(1, dtype=torch.int64, device=dev)
         self._check(lib().hj3d_select(self.h, C.byref(rel.c), arr, len(preds), out_pairs.data_ptr(),
                                       count.data_ptr()), "hj3d_select")
         if not fetch:
@@ -780,8 +799,9 @@ class Context:
         """#dv of rel's keys (all < domain) on this GPU; synchronous."""
         torch = _torch()
         dev = f"cuda:{self.device}"
-        bm = torch.zeros((1, (domain + 31) // 32), dtype=torch.int32, device=dev)
-        cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+        with self.on_stream():
+            bm = torch.zeros((1, (domain + 31) // 32), dtype=torch.int32, device=dev)
+            cnt = torch.zeros(2, dtype=torch.int64, device=dev)
         self.key_bitmap(rel, domain, bm, cnt[1:])
         self.bitmap_or_popcount(bm, cnt[:1])
         self.sync()
@@ -818,7 +838,8 @@ class Context:
 
     def expected_fk_join(self, build: Rel, probe: Rel, n_keys: int, swap: bool = False) -> dict:
         torch = _torch()
-        res = torch.zeros(8, dtype=torch.int64, device=f"cuda:{self.device}")
+        with self.on_stream():
+            res = torch.zeros(8, dtype=torch.int64, device=f"cuda:{self.device}")
         self._check(lib().hj3d_expected_fk_join(self.h, C.byref(build.c), C.byref(probe.c), n_keys, int(swap),
                                                 res.data_ptr()), "hj3d_expected_fk_join")
         self.sync()
@@ -828,7 +849,8 @@ class Context:
         """Expected key/FK aggregates for build keys made by gen_keys(n_keys, key_seed); accumulates
         into the device int64[8] tensor `res` when given (multi-GPU), else returns a dict."""
         torch = _torch()
-        r = res if res is not None else torch.zeros(8, dtype=torch.int64, device=f"cuda:{self.device}")
+        with self.on_stream():
+            r = res if res is not None else torch.zeros(8, dtype=torch.int64, device=f"cuda:{self.device}")
         self._check(lib().hj3d_expected_fk_join_gen(self.h, C.byref(probe.c), n_keys, key_seed, int(swap),
                                                     r.data_ptr()), "hj3d_expected_fk_join_gen")
         if res is not None:
@@ -982,8 +1004,9 @@ class Comm:
     def allreduce_u64(self, values, op: int = RED_SUM):
         """u64 counters reduced over ranks (mod 2^64 for the sum). Synchronous."""
         torch = _torch()
-        t = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in (int(x) & MASK64 for x in values)],
-                         dtype=torch.int64, device=f"cuda:{self.ctx.device}")
+        with self.ctx.on_stream():  # (the upload is ordered before the collective)
+            t = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in (int(x) & MASK64 for x in values)],
+                             dtype=torch.int64, device=f"cuda:{self.ctx.device}")
         self.ctx._check(lib().hj3d_comm_allreduce_u64(self.ctx.h, t.data_ptr(), t.numel(), op),
                         "hj3d_comm_allreduce_u64")
         self.ctx.sync()
@@ -993,8 +1016,9 @@ class Comm:
         torch = _torch()
         v = int(value) & MASK64
         dev = f"cuda:{self.ctx.device}"
-        src = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v], dtype=torch.int64, device=dev)
-        dst = torch.empty(self.world, dtype=torch.int64, device=dev)
+        with self.ctx.on_stream():
+            src = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v], dtype=torch.int64, device=dev)
+            dst = torch.empty(self.world, dtype=torch.int64, device=dev)
         self.ctx._check(lib().hj3d_comm_allgather(self.ctx.h, src.data_ptr(), dst.data_ptr(), 8), "hj3d_comm_allgather")
         self.ctx.sync()
         return [int(x) & MASK64 for x in dst.cpu().tolist()]
@@ -1082,7 +1106,8 @@ class Table:
         n_mains = None
         if out is None:  # (the main-record count is read from the table: synchronous)
             n_mains = self.size()[1] if self.kind == HJ3D_NESTED else 0
-            out = torch.empty((n_mains, 3), dtype=torch.int64, device=f"cuda:{self.ctx.device}")
+            with self.ctx.on_stream():
+                out = torch.empty((n_mains, 3), dtype=torch.int64, device=f"cuda:{self.ctx.device}")
         elif not out.is_cuda or out.dtype != torch.int64 or out.dim() != 2 or out.shape[1] != 3 or not out.is_contiguous():
             raise ValueError("out must be a contiguous (cap, 3) int64 device tensor")
         self.ctx._check(lib().hj3d_group_agg(self.ctx.h, self.h, C.byref(rel.c), 4 * word, int(bool(signed)),

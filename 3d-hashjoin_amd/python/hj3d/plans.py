@@ -12,7 +12,22 @@ returns the counters the reference writes to its measurement CSV:
 """
 from __future__ import annotations
 
+import functools
+
 from . import HJ3D_CHAIN, HJ3D_NESTED, Context, Rel, Table
+
+
+def _on_ctx_stream(plan):
+    """A plan that allocates or fills device tensors of its own (partition counters, bitmaps, the
+    buffers between two operators) runs with the context's stream as torch's current one
+    (Context.on_stream): the fills are then ordered before the library's writes, and a host read of such
+    a tensor is ordered after them."""
+    @functools.wraps(plan)
+    def run(ctx, *args, **kwargs):
+        with ctx.on_stream():
+            return plan(ctx, *args, **kwargs)
+    return run
+
 
 # plan -> (table kind, build relation "R"|"S", build key word, probe key word, unique, unnest)
 EXP1_PLANS = {
@@ -75,6 +90,7 @@ def merge_shard_stats(parts: list) -> dict:
     return out
 
 
+@_on_ctx_stream
 def exp1_plan_sharded(ctx: Context, plan: str, R, S, nb: int, parts: int, out=None, stats: bool = True,
                       checksum: bool = True, timing: list | None = None, single_pass: bool = False) -> dict:
     """The multi-GPU split of SURVEY §8(e) emulated on ONE device, owner after owner: both
@@ -167,6 +183,7 @@ def exp1_plan_sharded(ctx: Context, plan: str, R, S, nb: int, parts: int, out=No
     return res
 
 
+@_on_ctx_stream
 def num_distinct_sharded(ctx: Context, rel: Rel, domain: int, parts: int) -> int:
     """The distributed #dv pre-pass of SURVEY §8(e) step 1 (hj3d.dist.num_distinct) emulated on ONE
     device: `parts` ranks each hold a contiguous 1/parts of rel and set the bits of their keys in a
@@ -244,6 +261,7 @@ def exp4_plan(ctx: Context, plan: str, R, S, T, nb: int, fused: bool = True, out
     return r
 
 
+@_on_ctx_stream
 def exp4_plan_chained(ctx: Context, R, S, T, nb, keys=(0, 0), out=None, checksum: bool = True) -> dict:
     """Experiment-4 Ndu from the separate operators (main_experiment4.cc:847-850 as written: the second
     nested probe takes the first one's output): two nested tables on S.a and T.a, then
@@ -313,6 +331,7 @@ def _star_chain(ctx: Context, R, builds, nb, keys, filters):
     return tables, cur, levels
 
 
+@_on_ctx_stream
 def star_plan_chained(ctx: Context, R, builds, nb, keys, out=None, checksum: bool = True, filters=None) -> dict:
     """A k-way star Ndu from the separate operators, AlgNestJoinProbe / AlgUnnestHt stacked k deep
     (algebra.hh:435-541; experiment 4 is k = 2): one nested table per (relation, key word) in `builds`
@@ -333,6 +352,7 @@ def star_plan_chained(ctx: Context, R, builds, nb, keys, out=None, checksum: boo
     return res
 
 
+@_on_ctx_stream
 def star_plan_aggregate(ctx: Context, R, builds, nb, keys, aggregate, out=None, filters=None) -> dict:
     """star_plan_chained's chain (same R, builds, nb, keys, filters) ending in aggregates over the join
     result instead of the result itself, computed without unnesting. aggregate: [("count",), ("sum" | "min"
@@ -375,6 +395,7 @@ def merge_exp4(parts: list) -> dict:
     return out
 
 
+@_on_ctx_stream
 def exp4_plan_sharded(ctx: Context, plan: str, R, S, T, nb: int, parts: int, timing: list | None = None,
                       checksum: bool = True, out=None) -> dict:
     """Experiment 4 split as the multi-GPU strand splits it (Ndu co-partitions R, S and T

@@ -159,6 +159,13 @@ uint64_t hj3d_mix64(uint64_t z);
  * (default) stream, i.e. the stream torch uses unless told otherwise. */
 hj3d_status hj3d_ctx_create(int device, void* hip_stream, hj3d_ctx** out);
 void        hj3d_ctx_destroy(hj3d_ctx* ctx);
+/* Later calls are enqueued on hip_stream (NULL: the null stream). The call inserts NO ordering between
+ * the old and the new stream: work enqueued before it stays on the old stream, and nothing on the new
+ * stream waits for it. Before a call on the new stream uses what calls on the old one produced (a built
+ * table, the result slot, the context's scratch), the caller orders the new stream after the old one
+ * (an event recorded on the old and waited for on the new stream, or hj3d_ctx_sync before the switch).
+ * A nested build still pending is finished by a host wait on the build's own event, so its counts are
+ * safe; the table's device arrays are not. hj3d_ctx_stream returns the current handle. */
 hj3d_status hj3d_ctx_set_stream(hj3d_ctx* ctx, void* hip_stream);
 void*       hj3d_ctx_stream(const hj3d_ctx* ctx);
 hj3d_status hj3d_ctx_sync(hj3d_ctx* ctx); /* synchronous: waits for the stream */
