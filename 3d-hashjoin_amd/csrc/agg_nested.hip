@@ -9,17 +9,15 @@
 //                    records of the whole batch, then the gcol words that depend on them (one 8-byte
 //                    field per spec), then the values: stored as one row of 8 nspec B per input tuple
 //                    (non-temporal, dense, input order, below out_cap) and folded into the totals.
-// Liveness and the magnitude rule are k_unn_slots': a ref not below its table's main-record count kills
-// the tuple (nothing is read through it), the multiplies saturate, and the products are summed a second
-// time in two halves.
+// Liveness is k_unn_slots': a ref not below its table's main-record count kills the tuple (nothing is
+// read through it). The products follow the magnitude rule (nested_tuple.hpp).
 // The result slot (kAggnWords u64 words, zeroed before the launch): n_live, c_top, the sum of prod >> 32,
 // the sum of the low words, the flagged tuples, then the COUNT / SUM totals (added), then the MIN / MAX
 // totals as keys folded with atomicMax, so that the zeroed word is the identity: a value's key is the
 // value with the sign bit flipped for a signed spec (unsigned order = the value's order); MAX folds the
 // key, MIN its complement (agg_total_decode).
 // Algorithmic bytes per tuple: 4 (K + 1) read, 16 per ref, 8 per spec read (24: its record), 8 nspec written.
-#include "hj3d_internal.hpp"
-#include "row_words.hpp"
+#include "nested_tuple.hpp"
 
 namespace hj3d {
 namespace {
@@ -91,21 +89,15 @@ __global__ __launch_bounds__(kBlock) void k_aggn(const uint32_t* __restrict__ in
       }
 #pragma unroll
     for (int b = 0; b < B; ++b) {
-      // P, saturating (k_unn_slots' rule)
+      // P, by the magnitude rule
       uint64_t p = live[b] ? 1u : 0u;
       bool sat = false;
 #pragma unroll
-      for (int j = 0; j < K; ++j) {
-        sat = sat || __umul64hi(p, uint64_t(len[b][j])) != 0;
-        p *= len[b][j];
-      }
-      sat = sat || (p >> 63) != 0;
-      if (sat) p = 0;
+      for (int j = 0; j < K; ++j) product_step(p, sat, len[b][j]);
+      p = product_end(p, sat);
       add[0] += live[b] ? 1u : 0u;
-      add[1] += p;
-      add[2] += p >> 32;
-      add[3] += p & 0xFFFFFFFFull;
-      add[4] += sat ? 1u : 0u;
+      add[kAggnCTop] += p;
+      magnitude_add(add + kAggnHi, p, sat);
       const uint64_t i = i0 + uint64_t(b) * kBlock;
       uint64_t* row = out + uint64_t(a.nspec) * i;
 #pragma unroll
@@ -190,14 +182,7 @@ hipError_t agg_nested(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t k, con
     a.sgn[q] = specs[q].is_signed != 0;
   }
   const uint32_t* tin = static_cast<const uint32_t*>(in);
-  switch (k) {
-    case 1: return run<1>(ctx, tin, n, a, flags, out, out_cap, res, s);
-    case 2: return run<2>(ctx, tin, n, a, flags, out, out_cap, res, s);
-    case 3: return run<3>(ctx, tin, n, a, flags, out, out_cap, res, s);
-    case 4: return run<4>(ctx, tin, n, a, flags, out, out_cap, res, s);
-    case 5: return run<5>(ctx, tin, n, a, flags, out, out_cap, res, s);
-    default: return run<6>(ctx, tin, n, a, flags, out, out_cap, res, s);
-  }
+  return dispatch_width<1, kMax>(k, [&](auto K) { return run<K()>(ctx, tin, n, a, flags, out, out_cap, res, s); });
 }
 
 }  // namespace hj3d

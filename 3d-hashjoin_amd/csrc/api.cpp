@@ -11,6 +11,7 @@
 #include <new>
 
 #include "hj3d_internal.hpp"
+#include "nested_tuple.hpp"
 
 #include <atomic>
 #include <chrono>
@@ -272,6 +273,33 @@ hj3d_status probe_args_ok(hj3d_ctx* ctx, const char* entry, const hj3d_table* t,
   if (const hj3d_status st = emit_buffer_ok(ctx, entry, flags, out_dev, out_cap); st != HJ3D_OK) return st;
   if ((flags & HJ3D_PROBE_UNNEST) && t->desc.kind != HJ3D_NESTED) return fail_in(ctx, entry, "UNNEST needs a nested table");
   if (!mainref_ok(t, flags)) return fail_in(ctx, entry, "MAINREF needs a nested table, EMIT and no UNNEST");
+  return HJ3D_OK;
+}
+
+// The same for the entries over stored nested tuples {a, ref_1 .. ref_k}: the n input tuples, the
+// output buffer's alignment (4: tuples, 8: aggregate rows), and the k tables they refer to.
+hj3d_status nested_input_ok(hj3d_ctx* ctx, const char* entry, const void* nested_dev, uint64_t n) {
+  return (n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32) ? fail_in(ctx, entry, "invalid input")
+                                                                                : HJ3D_OK;
+}
+hj3d_status out_aligned(hj3d_ctx* ctx, const char* entry, const void* out_dev, uintptr_t align) {
+  return uintptr_t(out_dev) & (align - 1) ? fail_in(ctx, entry, "misaligned output buffer") : HJ3D_OK;
+}
+hj3d_status tables_given(hj3d_ctx* ctx, const char* entry, const hj3d_table* const* tables, uint32_t k) {
+  for (uint32_t i = 0; i < k; ++i)
+    if (!tables[i]) return fail_in(ctx, entry, "a null table");
+  return HJ3D_OK;
+}
+// (a null entry passes: hj3d_select_nested's tables are optional, the others ran tables_given before)
+hj3d_status tables_nested(hj3d_ctx* ctx, const char* entry, const hj3d_table* const* tables, uint32_t k) {
+  for (uint32_t i = 0; i < k; ++i)
+    if (tables[i] && tables[i]->desc.kind != HJ3D_NESTED) return fail_in(ctx, entry, "needs nested tables");
+  return HJ3D_OK;
+}
+hj3d_status resolve_all(hj3d_ctx* ctx, const char* entry, const hj3d_table* const* tables, uint32_t k) {
+  for (uint32_t i = 0; i < k; ++i)
+    if (tables[i])
+      if (hipError_t re = resolve(ctx, tables[i]); re != hipSuccess) return from_hip(ctx, re, entry);
   return HJ3D_OK;
 }
 
@@ -840,40 +868,40 @@ hj3d_status hj3d_unnest(hj3d_ctx* ctx, const hj3d_table* t, const void* nested_d
 
 hj3d_status hj3d_unnest2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const void* nested_dev,
                          uint64_t n, uint32_t flags, void* out_dev, uint64_t out_cap) {
+  const char* const me = "hj3d_unnest2";
+  const hj3d_table* const tables[2] = {ts, tt};
   if (!ctx || !ts || !tt) return HJ3D_EINVAL;
-  if (const hj3d_status st = unnest_flags_ok(ctx, "hj3d_unnest2", flags); st != HJ3D_OK) return st;
-  if (ts->desc.kind != HJ3D_NESTED || tt->desc.kind != HJ3D_NESTED)
-    return fail(ctx, HJ3D_EINVAL, "hj3d_unnest2: needs two nested tables");
-  if ((n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32))
-    return fail(ctx, HJ3D_EINVAL, "hj3d_unnest2: invalid input");
-  if ((flags & HJ3D_PROBE_EMIT) && ((!out_dev && out_cap) || (uintptr_t(out_dev) & 3)))
-    return fail(ctx, HJ3D_EINVAL, "hj3d_unnest2: EMIT without (aligned) buffer");
-  if (hipError_t re = resolve(ctx, ts); re != hipSuccess) return from_hip(ctx, re, "hj3d_unnest2");
-  if (hipError_t re = resolve(ctx, tt); re != hipSuccess) return from_hip(ctx, re, "hj3d_unnest2");
+  if (const hj3d_status st = unnest_flags_ok(ctx, me, flags); st != HJ3D_OK) return st;
+  if (const hj3d_status st = tables_nested(ctx, me, tables, 2); st != HJ3D_OK) return st;
+  if (const hj3d_status st = nested_input_ok(ctx, me, nested_dev, n); st != HJ3D_OK) return st;
+  // (the buffer of a call without EMIT is not looked at)
+  if (const hj3d_status st = out_aligned(ctx, me, (flags & HJ3D_PROBE_EMIT) ? out_dev : nullptr, 4); st != HJ3D_OK)
+    return st;
+  if (const hj3d_status st = emit_buffer_ok(ctx, me, flags, out_dev, out_cap); st != HJ3D_OK) return st;
+  if (const hj3d_status st = resolve_all(ctx, me, tables, 2); st != HJ3D_OK) return st;
   PhaseTimer tm(ctx, HJ3D_T_PROBE);
   const hipError_t e =
       unnest_triples(ctx, ts, tt, nested_dev, n, flags, out_dev, out_cap, ctx->res.as<uint64_t>(), ctx->stream);
   note_probe2(ctx, flags, out_cap);
-  return from_hip(ctx, e, "hj3d_unnest2");
+  return from_hip(ctx, e, me);
 }
 
-// hj3d_probe_ref (max_words 2: the {a} / {a, ref} kernels of probe_ref.hip) and hj3d_probe_refn
-// (max_words HJ3D_NEST_MAX: probe_refn.hip's, one instantiation per width)
+// hj3d_probe_ref (max_words 2) and hj3d_probe_refn (max_words HJ3D_NEST_MAX): one entry over
+// probe_ref.hip's kernels, one instantiation per width
 static hj3d_status probe_ref_any(hj3d_ctx* ctx, const char* me, uint32_t max_words, const hj3d_table* t,
                                  const hj3d_rel* base, const void* nested_dev, uint64_t n, uint32_t in_words,
                                  uint32_t flags, void* out_dev, uint64_t out_cap) {
   if (!ctx || !t || !base) return HJ3D_EINVAL;
-  const bool wide = max_words > 2;
   if (const hj3d_status st = unnest_flags_ok(ctx, me, flags); st != HJ3D_OK) return st;
-  if (t->desc.kind != HJ3D_NESTED) return fail_in(ctx, me, "needs a nested table");
+  if (const hj3d_status st = tables_nested(ctx, me, &t, 1); st != HJ3D_OK) return st;
   if (in_words < 1 || in_words > max_words)
-    return fail_in(ctx, me, wide ? "in_words must be 1 .. HJ3D_NEST_MAX" : "in_words must be 1 or 2");
+    return fail_in(ctx, me, max_words > 2 ? "in_words must be 1 .. HJ3D_NEST_MAX" : "in_words must be 1 or 2");
   if (!rel_ok(base) || base->row_off != HJ3D_ROW_IMPLICIT)
     return fail_in(ctx, me, "invalid base relation (implicit rows only)");
-  if ((n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32)) return fail_in(ctx, me, "invalid input");
-  if (uintptr_t(out_dev) & 3) return fail_in(ctx, me, "misaligned output buffer");
+  if (const hj3d_status st = nested_input_ok(ctx, me, nested_dev, n); st != HJ3D_OK) return st;
+  if (const hj3d_status st = out_aligned(ctx, me, out_dev, 4); st != HJ3D_OK) return st;
   if (const hj3d_status st = emit_buffer_ok(ctx, me, flags, out_dev, out_cap); st != HJ3D_OK) return st;
-  if (hipError_t re = resolve(ctx, t); re != hipSuccess) return from_hip(ctx, re, me);
+  if (const hj3d_status st = resolve_all(ctx, me, &t, 1); st != HJ3D_OK) return st;
   uint64_t* res = ctx->res.as<uint64_t>();
   if (n == 0) {
     const hipError_t e = hipMemsetAsync(res, 0, kResFields * sizeof(uint64_t), ctx->stream);
@@ -891,8 +919,7 @@ static hj3d_status probe_ref_any(hj3d_ctx* ctx, const char* me, uint32_t max_wor
   uint2* dense = ctx->scratch[kScrRefDense].as<uint2>();
   {
     PhaseTimer tm(ctx, HJ3D_T_PROBE);
-    e = (wide ? probe_refn_gather : probe_ref_gather)(ctx, nested_dev, n, in_words, *base, stage, dense, cursor,
-                                                      ctx->stream);
+    e = probe_refn_gather(ctx, nested_dev, n, in_words, *base, stage, dense, cursor, ctx->stream);
   }
   if (e != hipSuccess) return from_hip(ctx, e, me);
   // the live tuples probe t: the selection on the `live` word is fused into the probe partitioner on
@@ -907,8 +934,7 @@ static hj3d_status probe_ref_any(hj3d_ctx* ctx, const char* me, uint32_t max_wor
     return st;
   {
     PhaseTimer tm(ctx, HJ3D_T_PROBE);
-    e = (wide ? probe_refn_compact : probe_ref_compact)(ctx, t, dense, n, nested_dev, in_words, flags, out_dev,
-                                                        out_cap, cursor, res, ctx->stream);
+    e = probe_refn_compact(ctx, t, dense, n, nested_dev, in_words, flags, out_dev, out_cap, cursor, res, ctx->stream);
     // the non-dense overflow convention: n_out against the capacity, on the stream
     if (e == hipSuccess) e = out_check(ctx, false, flags, out_cap);
   }
@@ -932,16 +958,13 @@ hj3d_status hj3d_unnestn(hj3d_ctx* ctx, const hj3d_table* const* tables, uint32_
   const char* const me = "hj3d_unnestn";
   if (!ctx || !tables) return HJ3D_EINVAL;
   if (k < 1 || k > HJ3D_NEST_MAX) return fail_in(ctx, me, "k must be 1 .. HJ3D_NEST_MAX");
-  for (uint32_t i = 0; i < k; ++i)
-    if (!tables[i]) return fail_in(ctx, me, "a null table");
+  if (const hj3d_status st = tables_given(ctx, me, tables, k); st != HJ3D_OK) return st;
   if (const hj3d_status st = unnest_flags_ok(ctx, me, flags); st != HJ3D_OK) return st;
-  for (uint32_t i = 0; i < k; ++i)
-    if (tables[i]->desc.kind != HJ3D_NESTED) return fail_in(ctx, me, "needs nested tables");
-  if ((n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32)) return fail_in(ctx, me, "invalid input");
-  if (uintptr_t(out_dev) & 3) return fail_in(ctx, me, "misaligned output buffer");
+  if (const hj3d_status st = tables_nested(ctx, me, tables, k); st != HJ3D_OK) return st;
+  if (const hj3d_status st = nested_input_ok(ctx, me, nested_dev, n); st != HJ3D_OK) return st;
+  if (const hj3d_status st = out_aligned(ctx, me, out_dev, 4); st != HJ3D_OK) return st;
   if (const hj3d_status st = emit_buffer_ok(ctx, me, flags, out_dev, out_cap); st != HJ3D_OK) return st;
-  for (uint32_t i = 0; i < k; ++i)
-    if (hipError_t re = resolve(ctx, tables[i]); re != hipSuccess) return from_hip(ctx, re, me);
+  if (const hj3d_status st = resolve_all(ctx, me, tables, k); st != HJ3D_OK) return st;
   if (hipError_t ae = ctx->resn.ensure(kUnnWords * sizeof(uint64_t)); ae != hipSuccess) return from_hip(ctx, ae, me);
   PhaseTimer tm(ctx, HJ3D_T_PROBE);
   const hipError_t e =
@@ -960,9 +983,8 @@ hj3d_status hj3d_unnestn_result(hj3d_ctx* ctx, hj3d_unnestn_res* out) {
   if (const hj3d_status st = read_slot(ctx, "hj3d_unnestn_result", ctx->resn.p, h, kUnnWords); st != HJ3D_OK) return st;
   out->n_in = ctx->resn_n;
   out->n_live = h[0];
-  // the magnitude rule: a product, or the total (from the sums of the products' halves: no carry is
-  // lost), at or beyond 2^63; the expansion did not run
-  if (h[kUnnFlag] != 0 || h[kUnnHi] + (h[kUnnLo] >> 32) >= (1ull << 31))
+  // the magnitude rule: the expansion did not run
+  if (magnitude_exceeded(h[kUnnFlag], h[kUnnHi], h[kUnnLo]))
     return fail(ctx, HJ3D_EUNSUPPORTED, "hj3d_unnestn: a tuple's product or c_top reaches 2^63");
   for (int j = 0; j < HJ3D_NEST_MAX; ++j) {
     out->c_unnest[j] = h[1 + j];
@@ -989,7 +1011,8 @@ hj3d_status hj3d_select_nested(hj3d_ctx* ctx, const void* nested_dev, uint64_t n
   if (base && (!rel_ok(base) || base->row_off != HJ3D_ROW_IMPLICIT))
     return fail_in(ctx, me, "invalid base relation (implicit rows only)");
   for (uint32_t i = 0; i < k; ++i) {
-    if (tables && tables[i] && tables[i]->desc.kind != HJ3D_NESTED) return fail_in(ctx, me, "needs nested tables");
+    if (tables)
+      if (const hj3d_status st = tables_nested(ctx, me, tables + i, 1); st != HJ3D_OK) return st;
     if (builds && builds[i].stride && (!rel_ok(&builds[i]) || builds[i].row_off != HJ3D_ROW_IMPLICIT))
       return fail_in(ctx, me, "invalid build relation (implicit rows only)");
   }
@@ -1009,12 +1032,10 @@ hj3d_status hj3d_select_nested(hj3d_ctx* ctx, const void* nested_dev, uint64_t n
     }
     if (rel ? !sel_ok(rel, &q.pred, 1) : q.pred.op > HJ3D_SEL_RANGE) return fail_in(ctx, me, "invalid predicate");
   }
-  if ((n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32)) return fail_in(ctx, me, "invalid input");
-  if (uintptr_t(out_dev) & 3) return fail_in(ctx, me, "misaligned output buffer");
+  if (const hj3d_status st = nested_input_ok(ctx, me, nested_dev, n); st != HJ3D_OK) return st;
+  if (const hj3d_status st = out_aligned(ctx, me, out_dev, 4); st != HJ3D_OK) return st;
   if (const hj3d_status st = emit_buffer_ok(ctx, me, flags, out_dev, out_cap); st != HJ3D_OK) return st;
-  for (uint32_t i = 0; tables && i < k; ++i)
-    if (tables[i])
-      if (hipError_t re = resolve(ctx, tables[i]); re != hipSuccess) return from_hip(ctx, re, me);
+  if (const hj3d_status st = resolve_all(ctx, me, tables, tables ? k : 0); st != HJ3D_OK) return st;
   PhaseTimer tm(ctx, HJ3D_T_PROBE);
   hipError_t e = select_nested(ctx, nested_dev, n, k, base, tables, builds, preds, npred, flags, out_dev, out_cap,
                                ctx->res.as<uint64_t>(), ctx->stream);
@@ -1048,14 +1069,12 @@ hj3d_status hj3d_agg_nested(hj3d_ctx* ctx, const void* nested_dev, uint64_t n, u
   const char* const me = "hj3d_agg_nested";
   if (!ctx || !tables) return HJ3D_EINVAL;
   if (k < 1 || k > HJ3D_NEST_MAX) return fail_in(ctx, me, "k must be 1 .. HJ3D_NEST_MAX");
-  for (uint32_t i = 0; i < k; ++i)
-    if (!tables[i]) return fail_in(ctx, me, "a null table");
+  if (const hj3d_status st = tables_given(ctx, me, tables, k); st != HJ3D_OK) return st;
   if (nspec < 1 || nspec > HJ3D_AGG_MAX || !specs) return fail_in(ctx, me, "nspec must be 1 .. HJ3D_AGG_MAX");
   if (flags & ~HJ3D_PROBE_EMIT) return fail_in(ctx, me, "flags other than EMIT");
-  for (uint32_t i = 0; i < k; ++i)
-    if (tables[i]->desc.kind != HJ3D_NESTED) return fail_in(ctx, me, "needs nested tables");
-  if ((n && !nested_dev) || (uintptr_t(nested_dev) & 3) || n >= (1ull << 32)) return fail_in(ctx, me, "invalid input");
-  if (uintptr_t(out_dev) & 7) return fail_in(ctx, me, "misaligned output buffer");
+  if (const hj3d_status st = tables_nested(ctx, me, tables, k); st != HJ3D_OK) return st;
+  if (const hj3d_status st = nested_input_ok(ctx, me, nested_dev, n); st != HJ3D_OK) return st;
+  if (const hj3d_status st = out_aligned(ctx, me, out_dev, 8); st != HJ3D_OK) return st;
   if (const hj3d_status st = emit_buffer_ok(ctx, me, flags, out_dev, out_cap); st != HJ3D_OK) return st;
   for (uint32_t q = 0; q < nspec; ++q) {
     const hj3d_agg_spec& sp = specs[q];
@@ -1064,8 +1083,7 @@ hj3d_status hj3d_agg_nested(hj3d_ctx* ctx, const void* nested_dev, uint64_t n, u
       return fail_in(ctx, me, "a spec's slot outside 1 .. k (COUNT: not 0)");
     if (sp.op != HJ3D_AGG_COUNT && (!sp.gcol || (uintptr_t(sp.gcol) & 7))) return fail_in(ctx, me, "a spec without its column");
   }
-  for (uint32_t i = 0; i < k; ++i)
-    if (hipError_t re = resolve(ctx, tables[i]); re != hipSuccess) return from_hip(ctx, re, me);
+  if (const hj3d_status st = resolve_all(ctx, me, tables, k); st != HJ3D_OK) return st;
   for (uint32_t q = 0; q < nspec; ++q)  // (the main-record counts are known once the builds are finished)
     if (specs[q].op != HJ3D_AGG_COUNT && specs[q].gcol_n < tables[specs[q].slot - 1]->n_mains)
       return fail_in(ctx, me, "a column shorter than its table's main records");
@@ -1091,8 +1109,7 @@ hj3d_status hj3d_agg_nested_result(hj3d_ctx* ctx, hj3d_aggn_res* out) {
   if (const hj3d_status st = read_slot(ctx, "hj3d_agg_nested_result", ctx->resa.p, h, kAggnWords); st != HJ3D_OK) return st;
   out->n_in = ctx->resa_n;
   out->n_live = h[0];
-  // the magnitude rule of hj3d_unnestn
-  if (h[kAggnFlag] != 0 || h[kAggnHi] + (h[kAggnLo] >> 32) >= (1ull << 31))
+  if (magnitude_exceeded(h[kAggnFlag], h[kAggnHi], h[kAggnLo]))
     return fail(ctx, HJ3D_EUNSUPPORTED, "hj3d_agg_nested: a tuple's product or c_top reaches 2^63");
   out->c_top = h[kAggnCTop];
   for (uint32_t q = 0; q < HJ3D_AGG_MAX; ++q) {

@@ -456,22 +456,14 @@ hipError_t unnest_pairs(hj3d_ctx* ctx, const hj3d_table* t, const void* in, uint
 // unnest2.hip: hj3d_unnest2, n triples {a, ref_s, ref_t} expanded to {a, s_row, t_row} (clears res itself)
 hipError_t unnest_triples(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const void* in, uint64_t n,
                           uint32_t flags, void* out, uint64_t out_cap, uint64_t* res_dev, hipStream_t s);
-// probe_ref.hip: hj3d_probe_ref's two kernels around the nested probe. Gather: n input tuples of
-// `words` u32 ({a} / {a, ref}) to m = probe_ref_stage_tuples(n) >= n staging tuples {key of base row a,
+// probe_ref.hip: the two kernels of hj3d_probe_ref / hj3d_probe_refn around the nested probe, one
+// instantiation per tuple width. Gather: n input tuples of `words` u32 ({a, ref_1 ..}, 1..HJ3D_NEST_MAX
+// words) to m = probe_ref_stage_tuples(n) >= n staging tuples {key of base row a,
 // j, live} (stage, 3 m words; in a permuted order, the m - n padding tuples dead), the m dense slots
 // preset to {kInvalid, kInvalid} and *cursor zeroed. Compact: the m dense slots {j, main ref of t}
 // with a match to output tuples {input tuple j, main ref} at positions from *cursor (EMIT; at most
 // out_cap), res[4..8] (the row sums and pair hashes) replaced by those over a.
 uint64_t probe_ref_stage_tuples(uint64_t n);
-hipError_t probe_ref_gather(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t words, const hj3d_rel& base,
-                            uint32_t* stage, uint2* dense, unsigned long long* cursor, hipStream_t s);
-hipError_t probe_ref_compact(hj3d_ctx* ctx, const hj3d_table* t, const uint2* dense, uint64_t n, const void* in,
-                             uint32_t words, uint32_t flags, void* out, uint64_t out_cap, unsigned long long* cursor,
-                             uint64_t* res_dev, hipStream_t s);
-// probe_refn.hip: the same two kernels for tuples of 1..HJ3D_NEST_MAX words {a, ref_1 ..} (hj3d_probe_refn);
-// staging order, dense slots and cursor as above (probe_ref_mult: the staging permutation's multiplier
-// for ng groups)
-uint64_t probe_ref_mult(uint64_t ng);
 hipError_t probe_refn_gather(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t words, const hj3d_rel& base,
                              uint32_t* stage, uint2* dense, unsigned long long* cursor, hipStream_t s);
 hipError_t probe_refn_compact(hj3d_ctx* ctx, const hj3d_table* t, const uint2* dense, uint64_t n, const void* in,

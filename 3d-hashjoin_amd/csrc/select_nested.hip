@@ -18,11 +18,11 @@
 //   k_nsel_write<W, EMIT> reads the masks (2 B per 16 tuples), not the relations; ranks by ballot as
 //                         k_sel_write (all of items < j first, then the lower waves at item j: input
 //                         order), reloads the passing rows and stores them at tile offset + rank
-//                         below out_cap; folds sum_a and, with CHECKSUM, the row hash.
+//                         below out_cap; folds sum_a and, with CHECKSUM, the row hash (row_hash,
+//                         nested_tuple.hpp).
 // Algorithmic bytes per tuple: 4 (k + 1) read, 4 per base word, 16 per slot used, 4 per FIRST word,
 // 4 (k + 1) read again and 4 (k + 1) written per survivor.
-#include "hj3d_internal.hpp"
-#include "row_words.hpp"
+#include "nested_tuple.hpp"
 
 namespace hj3d {
 namespace {
@@ -212,14 +212,7 @@ __global__ __launch_bounds__(kBlock) void k_nsel_write(const uint32_t* __restric
       load_row<W>(in + uint64_t(W) * i, v);
       acc[0] += v[0];
       if (ck) {
-        uint64_t h;
-        if constexpr (W == 1) {
-          h = mix64(uint64_t(v[0]));
-        } else {
-          h = pair_hash(v[0], v[1]);
-#pragma unroll
-          for (int q = 2; q < W; ++q) h = mix64(h ^ uint64_t(v[q]));
-        }
+        const uint64_t h = row_hash(v);
         acc[3] += h;
         acc[4] ^= h;
       }
@@ -290,15 +283,7 @@ hipError_t select_nested(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t k, 
     a.s[j].bound = t ? uint32_t(t->n_mains < kInvalid ? t->n_mains : kInvalid) : kInvalid;
     a.s[j].main = t ? t->main.as<const uint4>() : nullptr;
   }
-  switch (k) {
-    case 0: return run<1>(ctx, in, n, a, flags, out, out_cap, res, s);
-    case 1: return run<2>(ctx, in, n, a, flags, out, out_cap, res, s);
-    case 2: return run<3>(ctx, in, n, a, flags, out, out_cap, res, s);
-    case 3: return run<4>(ctx, in, n, a, flags, out, out_cap, res, s);
-    case 4: return run<5>(ctx, in, n, a, flags, out, out_cap, res, s);
-    case 5: return run<6>(ctx, in, n, a, flags, out, out_cap, res, s);
-    default: return run<7>(ctx, in, n, a, flags, out, out_cap, res, s);
-  }
+  return dispatch_width<1, kMax + 1>(k + 1, [&](auto W) { return run<W()>(ctx, in, n, a, flags, out, out_cap, res, s); });
 }
 
 }  // namespace hj3d

@@ -8,21 +8,18 @@
 //   k_un2_slots   one slot per input triple: its product |S group| * |T group| (u64; 0 when a ref is
 //                 invalid) and {a, sub_off_s, sub_off_t, |S group|}: 12 B read, 24 B written per triple
 //   exclusive_scan_u64 of the products
-//   k_un2_expand  output-parallel: a workgroup takes kChunk consecutive OUTPUTS, finds the slots
-//                 they belong to (two binary searches over the scanned offsets, then the chunk's
-//                 offsets staged in LDS) and each thread writes outputs tid, tid + 256, ...: 12-B
-//                 stores of consecutive lanes are consecutive, and a hot pair of groups (a product of
-//                 millions) is spread over product / kChunk workgroups.
+//   k_un2_expand  output-parallel (for_each_output, nested_tuple.hpp, shared with unnestn.hip): a
+//                 workgroup takes kChunk consecutive OUTPUTS and each thread writes outputs tid,
+//                 tid + 256, ...: 12-B stores of consecutive lanes are consecutive, and a hot pair of
+//                 groups (a product of millions) is spread over product / kChunk workgroups.
 // Counters as exp4.hip's Ndu: c_unnest_1 += |T group|, c_unnest_2 = c_top += the product.
-#include "hj3d_internal.hpp"
+#include "nested_tuple.hpp"
 
 namespace hj3d {
 namespace {
 
 constexpr int kF = 12;  // hj3d_probe2_res: c_probe_rs, cmp_rs, c_probe_rt, cmp_rt, unnest_1, unnest_2, top,
                         // sum_a, sum_b, sum_c, sum_h, xor_h
-constexpr uint32_t kChunk = 2048;       // outputs per workgroup and step (8 per thread)
-constexpr uint32_t kChunkSlots = 2048;  // slot offsets of a chunk staged in LDS (more: searched in HBM)
 
 typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 typedef u32x3 u32x3_a4 __attribute__((aligned(4)));  // a triple is 4-byte aligned only
@@ -50,76 +47,41 @@ __global__ __launch_bounds__(kBlock) void k_un2_slots(const uint32_t* __restrict
   block_flush<kF, 1>(a, res);
 }
 
-// largest q in [lo, hi) with off[q] <= x, given off[lo] <= x < off[hi]
-template <typename T, typename I>
-__device__ __forceinline__ I last_le(const T* off, I lo, I hi, T x) {
-  while (hi - lo > 1) {
-    const I md = lo + (hi - lo) / 2;
-    if (off[md] <= x) lo = md;
-    else hi = md;
-  }
-  return lo;
-}
-
 template <bool EMIT>
 __global__ __launch_bounds__(kBlock) void k_un2_expand(const uint64_t* __restrict__ ooff, uint64_t n,
                                                        const uint4* __restrict__ slot,
                                                        const uint32_t* __restrict__ subS,
                                                        const uint32_t* __restrict__ subT, uint32_t* __restrict__ out,
                                                        uint64_t out_cap, uint64_t* __restrict__ res, bool ck) {
-  __shared__ uint32_t loff[kChunkSlots + 1];  // chunk-relative first output of the chunk's slots
-  __shared__ uint64_t qends[2];               // the slots of the chunk's first and last output
   uint64_t a[kF] = {0};
-  const uint64_t total = ooff[n];
-  for (uint64_t c = blockIdx.x; c * kChunk < total; c += gridDim.x) {  // (workgroup-uniform bounds)
-    const uint64_t o0 = c * kChunk;
-    const uint32_t len = uint32_t(total - o0 < kChunk ? total - o0 : kChunk);
-    // ooff[0] = 0 <= x < total = ooff[n]: the search's invariant holds for every output x; the slot
-    // it finds is not empty (ooff[q] <= x < ooff[q + 1])
-    if (threadIdx.x < 2) qends[threadIdx.x] = last_le<uint64_t, uint64_t>(ooff, 0, n, threadIdx.x ? o0 + len - 1 : o0);
-    __syncthreads();
-    const uint64_t q0 = qends[0], nq = qends[1] - q0 + 1;
-    const bool staged = nq <= kChunkSlots;
-    if (staged)
-      for (uint32_t j = threadIdx.x; j <= nq; j += kBlock) {
-        const uint64_t v = ooff[q0 + j];
-        loff[j] = v <= o0 ? 0u : (v - o0 >= len ? len : uint32_t(v - o0));  // loff[0] = 0, loff[nq] = len
-      }
-    __syncthreads();
-    for (uint32_t rel = threadIdx.x; rel < len; rel += kBlock) {
-      const uint64_t o = o0 + rel;
-      const uint64_t q = staged ? q0 + last_le<uint32_t, uint32_t>(loff, 0, uint32_t(nq), rel)
-                                : last_le<uint64_t, uint64_t>(ooff, q0, q0 + nq, o);
-      const uint64_t k = o - ooff[q];
-      const uint4 sl = slot[q];  // {a, sub_off_s, sub_off_t, |S group|}
-      // triple k of a slot: S row k % |S|, T row k / |S| (consecutive outputs read consecutive S rows)
-      uint32_t tq, sq;
-      if ((k >> 32) == 0) {
-        tq = uint32_t(k) / sl.w;
-        sq = uint32_t(k) - tq * sl.w;
-      } else {
-        tq = uint32_t(k / sl.w);
-        sq = uint32_t(k % sl.w);
-      }
-      const uint32_t sr = subS[sl.y + sq], tr = subT[sl.z + tq];
-      a[7] += sl.x;
-      a[8] += sr;
-      a[9] += tr;
-      if (ck) {
-        const uint64_t h = triple_hash(sl.x, sr, tr);
-        a[10] += h;
-        a[11] ^= h;
-      }
-      if (EMIT && o < out_cap) {
-        u32x3 v;
-        v.x = sl.x;
-        v.y = sr;
-        v.z = tr;
-        __builtin_nontemporal_store(v, reinterpret_cast<u32x3_a4*>(out + 3 * o));
-      }
+  for_each_output(ooff, n, [&](uint64_t o, uint64_t q, uint64_t k) {
+    const uint4 sl = slot[q];  // {a, sub_off_s, sub_off_t, |S group|}
+    // triple k of a slot: S row k % |S|, T row k / |S| (consecutive outputs read consecutive S rows)
+    uint32_t tq, sq;
+    if ((k >> 32) == 0) {
+      tq = uint32_t(k) / sl.w;
+      sq = uint32_t(k) - tq * sl.w;
+    } else {
+      tq = uint32_t(k / sl.w);
+      sq = uint32_t(k % sl.w);
     }
-    __syncthreads();  // loff / qends are rewritten by the next chunk
-  }
+    const uint32_t sr = subS[sl.y + sq], tr = subT[sl.z + tq];
+    a[7] += sl.x;
+    a[8] += sr;
+    a[9] += tr;
+    if (ck) {
+      const uint64_t h = triple_hash(sl.x, sr, tr);
+      a[10] += h;
+      a[11] ^= h;
+    }
+    if (EMIT && o < out_cap) {
+      u32x3 v;
+      v.x = sl.x;
+      v.y = sr;
+      v.z = tr;
+      __builtin_nontemporal_store(v, reinterpret_cast<u32x3_a4*>(out + 3 * o));
+    }
+  });
   block_flush<kF, 1>(a, res);
 }
 

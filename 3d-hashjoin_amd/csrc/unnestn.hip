@@ -7,29 +7,21 @@
 //   k_unn_slots<K>   one slot per input tuple: its product |G_1| * .. * |G_K| (u64; 0 when a ref is
 //                    invalid) and a record {a, sub_off_1 .. sub_off_K, |G_1| .. |G_{K-1}|} of 2 K words:
 //                    4 (K + 1) B and up to K main records read, 8 + 8 K B written per tuple. The
-//                    multiplies saturate: a tuple whose product reaches 2^63 counts into a flag word
-//                    (and gets the product 0), and the products are summed a second time in two halves
-//                    (sum of prod >> 32, sum of the low words), from which the total is known to stay
-//                    below 2^63 or not without a carry being lost.
+//                    products follow the magnitude rule (nested_tuple.hpp).
 //   exclusive_scan_u64 of the products
-//   k_unn_expand<K>  output-parallel, as k_un2_expand: a workgroup takes kChunk consecutive OUTPUTS,
-//                    finds their slots (two binary searches over the scanned offsets, then the chunk's
-//                    offsets staged in LDS; searched in HBM when the chunk spans more than kChunkSlots
-//                    slots) and each thread writes outputs tid, tid + 256, .. Output o of a slot
+//   k_unn_expand<K>  output-parallel, k_un2_expand's walk (for_each_output, nested_tuple.hpp): each
+//                    thread writes outputs tid, tid + 256, .. of a chunk. Output o of a slot
 //                    decomposes in mixed radix, group 1 the fastest digit: consecutive lanes read
 //                    consecutive sub rows of table 1 and store consecutive rows of 4 (K + 1) B.
 //                    It reads the magnitude words first and leaves when the counts are not exact.
 // Counters in the reference's order (the last table probed is unnested first):
 // c_unnest[j] += |G_K| * .. * |G_{K-j}|, c_top = c_unnest[K - 1].
-#include "hj3d_internal.hpp"
-#include "row_words.hpp"
+#include "nested_tuple.hpp"
 
 namespace hj3d {
 namespace {
 
 constexpr int kMax = HJ3D_NEST_MAX;
-constexpr uint32_t kChunk = 2048;       // outputs per workgroup and step (8 per thread)
-constexpr uint32_t kChunkSlots = 2048;  // slot offsets of a chunk staged in LDS (more: searched in HBM)
 
 // The device result slot (kUnnWords u64 words; hj3d_unnestn_result maps it to hj3d_unnestn_res):
 // words [0, kSF) are the slot kernel's, [kSF, kSF + kEF) the expand kernel's.
@@ -80,33 +72,18 @@ __global__ __launch_bounds__(kBlock) void k_unn_slots(const uint32_t* __restrict
     bool sat = false;
 #pragma unroll
     for (int j = K - 1; j >= 0; --j) {
-      sat = sat || __umul64hi(p, uint64_t(len[j])) != 0;
-      p *= len[j];
+      product_step(p, sat, len[j]);
       if (K - 1 - j < K - 1) a[1 + (K - 1 - j)] += p;  // (the last one below, once it is known to be exact)
     }
-    sat = sat || (p >> 63) != 0;
-    if (sat) p = 0;  // not expanded; the result reports HJ3D_EUNSUPPORTED
+    p = product_end(p, sat);  // (0: not expanded)
     cnt[i] = p;
     slot[i] = r;
     a[0] += live ? 1u : 0u;
     a[K] += p;
-    a[1 + kMax] += p;
-    a[2 + kMax] += p >> 32;
-    a[3 + kMax] += p & 0xFFFFFFFFull;
-    a[4 + kMax] += sat ? 1u : 0u;
+    a[kUnnCTop] += p;
+    magnitude_add(a + kUnnHi, p, sat);
   }
   block_flush<kSF, 0>(a, res);
-}
-
-// largest q in [lo, hi) with off[q] <= x, given off[lo] <= x < off[hi]
-template <typename T, typename I>
-__device__ __forceinline__ I last_le(const T* off, I lo, I hi, T x) {
-  while (hi - lo > 1) {
-    const I md = lo + (hi - lo) / 2;
-    if (off[md] <= x) lo = md;
-    else hi = md;
-  }
-  return lo;
 }
 
 template <int K, bool EMIT>
@@ -114,75 +91,48 @@ __global__ __launch_bounds__(kBlock) void k_unn_expand(const uint64_t* __restric
                                                        const SlotRec<K>* __restrict__ slot, UnnSubs tb,
                                                        uint32_t* __restrict__ out, uint64_t out_cap,
                                                        uint64_t* __restrict__ res, bool ck) {
-  __shared__ uint32_t loff[kChunkSlots + 1];  // chunk-relative first output of the chunk's slots
-  __shared__ uint64_t qends[2];               // the slots of the chunk's first and last output
-  // the magnitude rule: a product or the total at or beyond 2^63 (the scanned offsets then mean
-  // nothing): nothing is walked (these words are the slot kernel's; this kernel does not write them)
-  if (res[kUnnFlag] != 0 || res[kUnnHi] + (res[kUnnLo] >> 32) >= (1ull << 31)) return;
+  // the magnitude rule: the scanned offsets then mean nothing, and nothing is walked (these words are
+  // the slot kernel's; this kernel does not write them)
+  if (magnitude_exceeded(res[kUnnFlag], res[kUnnHi], res[kUnnLo])) return;
   uint64_t a[kEF] = {0};
-  uint64_t* const eres = res + kSF;
-  const uint64_t total = ooff[n];
-  for (uint64_t c = blockIdx.x; c * kChunk < total; c += gridDim.x) {  // (workgroup-uniform bounds)
-    const uint64_t o0 = c * kChunk;
-    const uint32_t len = uint32_t(total - o0 < kChunk ? total - o0 : kChunk);
-    // ooff[0] = 0 <= x < total = ooff[n]: the search's invariant holds for every output x; the slot
-    // it finds is not empty (ooff[q] <= x < ooff[q + 1])
-    if (threadIdx.x < 2) qends[threadIdx.x] = last_le<uint64_t, uint64_t>(ooff, 0, n, threadIdx.x ? o0 + len - 1 : o0);
-    __syncthreads();
-    const uint64_t q0 = qends[0], nq = qends[1] - q0 + 1;
-    const bool staged = nq <= kChunkSlots;
-    if (staged)
-      for (uint32_t j = threadIdx.x; j <= nq; j += kBlock) {
-        const uint64_t v = ooff[q0 + j];
-        loff[j] = v <= o0 ? 0u : (v - o0 >= len ? len : uint32_t(v - o0));  // loff[0] = 0, loff[nq] = len
+  for_each_output(ooff, n, [&](uint64_t o, uint64_t q, uint64_t x) {
+    const SlotRec<K> sl = slot[q];
+    // output x of a slot: digit j (its row in group j + 1) in mixed radix, group 1 the fastest
+    uint32_t d[K];
+    if ((x >> 32) == 0) {
+      uint32_t y = uint32_t(x);
+#pragma unroll
+      for (int j = 0; j < K - 1; ++j) {
+        const uint32_t qq = y / sl.w[1 + K + j];
+        d[j] = y - qq * sl.w[1 + K + j];
+        y = qq;
       }
-    __syncthreads();
-    for (uint32_t rel = threadIdx.x; rel < len; rel += kBlock) {
-      const uint64_t o = o0 + rel;
-      const uint64_t q = staged ? q0 + last_le<uint32_t, uint32_t>(loff, 0, uint32_t(nq), rel)
-                                : last_le<uint64_t, uint64_t>(ooff, q0, q0 + nq, o);
-      const uint64_t x = o - ooff[q];
-      const SlotRec<K> sl = slot[q];
-      // output x of a slot: digit j (its row in group j + 1) in mixed radix, group 1 the fastest
-      uint32_t d[K];
-      if ((x >> 32) == 0) {
-        uint32_t y = uint32_t(x);
+      d[K - 1] = y;
+    } else {
+      uint64_t y = x;
 #pragma unroll
-        for (int j = 0; j < K - 1; ++j) {
-          const uint32_t qq = y / sl.w[1 + K + j];
-          d[j] = y - qq * sl.w[1 + K + j];
-          y = qq;
-        }
-        d[K - 1] = y;
-      } else {
-        uint64_t y = x;
-#pragma unroll
-        for (int j = 0; j < K - 1; ++j) {
-          const uint64_t qq = y / sl.w[1 + K + j];
-          d[j] = uint32_t(y - qq * sl.w[1 + K + j]);
-          y = qq;
-        }
-        d[K - 1] = uint32_t(y);
+      for (int j = 0; j < K - 1; ++j) {
+        const uint64_t qq = y / sl.w[1 + K + j];
+        d[j] = uint32_t(y - qq * sl.w[1 + K + j]);
+        y = qq;
       }
-      uint32_t v[K + 1];
-      v[0] = sl.w[0];
-#pragma unroll
-      for (int j = 0; j < K; ++j) v[1 + j] = tb.sub[j][sl.w[1 + j] + d[j]];
-      a[0] += v[0];
-#pragma unroll
-      for (int j = 0; j < K; ++j) a[1 + j] += v[1 + j];
-      if (ck) {
-        uint64_t h = pair_hash(v[0], v[1]);
-#pragma unroll
-        for (int j = 1; j < K; ++j) h = mix64(h ^ uint64_t(v[1 + j]));
-        a[1 + kMax] += h;
-        a[2 + kMax] ^= h;
-      }
-      if (EMIT && o < out_cap) store_row<K + 1, true>(out + (K + 1) * o, v);
+      d[K - 1] = uint32_t(y);
     }
-    __syncthreads();  // loff / qends are rewritten by the next chunk
-  }
-  block_flush<kEF, 1>(a, eres);
+    uint32_t v[K + 1];
+    v[0] = sl.w[0];
+#pragma unroll
+    for (int j = 0; j < K; ++j) v[1 + j] = tb.sub[j][sl.w[1 + j] + d[j]];
+    a[0] += v[0];
+#pragma unroll
+    for (int j = 0; j < K; ++j) a[1 + j] += v[1 + j];
+    if (ck) {
+      const uint64_t h = row_hash(v);
+      a[1 + kMax] += h;
+      a[2 + kMax] ^= h;
+    }
+    if (EMIT && o < out_cap) store_row<K + 1, true>(out + (K + 1) * o, v);
+  });
+  block_flush<kEF, 1>(a, res + kSF);
 }
 
 template <int K>
@@ -222,15 +172,7 @@ hipError_t unnest_wide(hj3d_ctx* ctx, const hj3d_table* const* tables, uint32_t 
   z.add(res, kUnnWords);
   const hipError_t e = zero_words(z, s);
   if (e != hipSuccess || n == 0) return e;
-  switch (k) {
-    case 1: return run<1>(ctx, tables, in, n, flags, out, out_cap, res, s);
-    case 2: return run<2>(ctx, tables, in, n, flags, out, out_cap, res, s);
-    case 3: return run<3>(ctx, tables, in, n, flags, out, out_cap, res, s);
-    case 4: return run<4>(ctx, tables, in, n, flags, out, out_cap, res, s);
-    case 5: return run<5>(ctx, tables, in, n, flags, out, out_cap, res, s);
-    case 6: return run<6>(ctx, tables, in, n, flags, out, out_cap, res, s);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_width<1, kMax>(k, [&](auto K) { return run<K()>(ctx, tables, in, n, flags, out, out_cap, res, s); });
 }
 
 }  // namespace hj3d

@@ -266,14 +266,16 @@ def _words(t, words: int, what: str, rows: str = "n"):
     return (t.data_ptr() if t.shape[0] else None), t.shape[0]
 
 
-def _emit_args(out, words=None):
-    """(flag, ptr, cap) for an output tensor: PROBE_EMIT and its buffer, or nothing without one. words=None: a
-    buffer of 8-byte pairs (any shape); else a contiguous (cap, words) int32 device tensor."""
+def _emit_args(out, words=None, checksum=False):
+    """(flags, ptr, cap) for an output tensor: PROBE_EMIT and its buffer, or nothing without one. words=None: a
+    buffer of 8-byte pairs (any shape); else a contiguous (cap, words) int32 device tensor. checksum: the
+    flags carry PROBE_CHECKSUM too."""
+    ck = PROBE_CHECKSUM if checksum else 0
     if out is None:
-        return 0, None, 0
+        return ck, None, 0
     if words is None:
-        return PROBE_EMIT, out.data_ptr(), out.numel() * out.element_size() // 8
-    return (PROBE_EMIT,) + _words(out, words, "out", "cap")
+        return ck | PROBE_EMIT, out.data_ptr(), out.numel() * out.element_size() // 8
+    return (ck | PROBE_EMIT,) + _words(out, words, "out", "cap")
 
 
 class Rel:
@@ -458,8 +460,7 @@ class Context:
         out: a contiguous (cap, 3) int32 device tensor that receives the output triples
         (r_row, s_row, t_row), at most cap of them, in no specified order; c_top counts all, and the
         result's `overflow` tells whether some did not fit."""
-        emit, ptr, cap = _emit_args(out, 3)
-        flags = (PROBE_CHECKSUM if checksum else 0) | emit
+        flags, ptr, cap = _emit_args(out, 3, checksum)
         self._check(lib().hj3d_probe2(self.h, ts.h, tt.h, C.byref(rel.c), flags, ptr, cap), "hj3d_probe2")
         return self.probe2_result() if fetch else None
 
@@ -480,8 +481,7 @@ class Context:
         (None: counters and sums only). n_out counts all pairs; `overflow` tells whether some did not
         fit. checksum=False leaves out the pair hashes (sum_h, xor_h)."""
         ptr_in, n = _words(nested, 2, "nested")
-        emit, ptr, cap = _emit_args(out, 2)
-        flags = (PROBE_CHECKSUM if checksum else 0) | emit
+        flags, ptr, cap = _emit_args(out, 2, checksum)
         self._check(lib().hj3d_unnest(self.h, table.h, ptr_in, n, flags, ptr, cap), "hj3d_unnest")
         return self.probe_result() if fetch else None
 
@@ -491,8 +491,7 @@ class Context:
         expanded to every {a, s_row, t_row} of the two groups. out: a contiguous (cap, 3) int32 device
         tensor or None; the result is probe2's dict (c_unnest_1, c_unnest_2, c_top, sums, overflow)."""
         ptr_in, n = _words(nested, 3, "nested")
-        emit, ptr, cap = _emit_args(out, 3)
-        flags = (PROBE_CHECKSUM if checksum else 0) | emit
+        flags, ptr, cap = _emit_args(out, 3, checksum)
         self._check(lib().hj3d_unnest2(self.h, ts.h, tt.h, ptr_in, n, flags, ptr, cap), "hj3d_unnest2")
         return self.probe2_result() if fetch else None
 
@@ -506,16 +505,17 @@ class Context:
         device tensor that receives every matching tuple with the main ref of `table` appended
         (None: counters and sums only). n_probe = live tuples, n_matched = n_out = those with a
         match; `overflow` tells whether some did not fit."""
+        return self._probe_ref("hj3d_probe_ref", 2, "(n, 1) or (n, 2)", table, base, nested, out, checksum, fetch)
+
+    def _probe_ref(self, entry: str, max_words: int, shape: str, table, base, nested, out, checksum, fetch):
         torch = _torch()
         if not nested.is_cuda or nested.dtype not in (torch.int32, torch.uint32) or nested.dim() != 2 or \
-                nested.shape[1] not in (1, 2) or not nested.is_contiguous():
-            raise ValueError("nested must be a contiguous (n, 1) or (n, 2) int32 device tensor")
+                not 1 <= nested.shape[1] <= max_words or not nested.is_contiguous():
+            raise ValueError(f"nested must be a contiguous {shape} int32 device tensor")
         words = nested.shape[1]
         ptr_in, n = _words(nested, words, "nested")
-        emit, ptr, cap = _emit_args(out, words + 1)
-        flags = (PROBE_CHECKSUM if checksum else 0) | emit
-        self._check(lib().hj3d_probe_ref(self.h, table.h, C.byref(base.c), ptr_in, n, words, flags, ptr, cap),
-                    "hj3d_probe_ref")
+        flags, ptr, cap = _emit_args(out, words + 1, checksum)
+        self._check(getattr(lib(), entry)(self.h, table.h, C.byref(base.c), ptr_in, n, words, flags, ptr, cap), entry)
         return self.probe_result() if fetch else None
 
     # ---- wide nested tuples: the chain and the unnest over up to HJ3D_NEST_MAX tables ----
@@ -526,17 +526,8 @@ class Context:
         0xFFFFFFFF. out: a contiguous (cap, words + 1) int32 device tensor that receives every
         matching tuple with the main ref of `table` appended, so the output feeds probe_refn again
         or unnestn. The result is probe_ref's."""
-        torch = _torch()
-        if not nested.is_cuda or nested.dtype not in (torch.int32, torch.uint32) or nested.dim() != 2 or \
-                not 1 <= nested.shape[1] <= HJ3D_NEST_MAX or not nested.is_contiguous():
-            raise ValueError(f"nested must be a contiguous (n, 1..{HJ3D_NEST_MAX}) int32 device tensor")
-        words = nested.shape[1]
-        ptr_in, n = _words(nested, words, "nested")
-        emit, ptr, cap = _emit_args(out, words + 1)
-        flags = (PROBE_CHECKSUM if checksum else 0) | emit
-        self._check(lib().hj3d_probe_refn(self.h, table.h, C.byref(base.c), ptr_in, n, words, flags, ptr, cap),
-                    "hj3d_probe_refn")
-        return self.probe_result() if fetch else None
+        return self._probe_ref("hj3d_probe_refn", HJ3D_NEST_MAX, f"(n, 1..{HJ3D_NEST_MAX})", table, base, nested, out,
+                               checksum, fetch)
 
     def unnestn(self, tables, nested, out=None, checksum: bool = True, fetch: bool = True) -> Optional[dict]:
         """hj3d_unnestn: tuples {a, ref_1 .. ref_k} (a contiguous (n, k + 1) int32 device tensor; ref_i a
@@ -547,8 +538,7 @@ class Context:
         if not 1 <= k <= HJ3D_NEST_MAX:
             raise ValueError(f"unnestn takes 1..{HJ3D_NEST_MAX} tables")
         ptr_in, n = _words(nested, k + 1, "nested")
-        emit, ptr, cap = _emit_args(out, k + 1)
-        flags = (PROBE_CHECKSUM if checksum else 0) | emit
+        flags, ptr, cap = _emit_args(out, k + 1, checksum)
         th = (C.c_void_p * k)(*[t.h for t in tables])
         self._check(lib().hj3d_unnestn(self.h, th, k, ptr_in, n, flags, ptr, cap), "hj3d_unnestn")
         self._unnestn_k = k
@@ -636,8 +626,7 @@ class Context:
             if lst is not None and len(lst) != k:
                 raise ValueError(f"{what} must have one entry per ref ({k}) or be None")
         ptr_in, n = _words(nested, k + 1, "nested")
-        emit, ptr, cap = _emit_args(out, k + 1)
-        flags = (PROBE_CHECKSUM if checksum else 0) | emit
+        flags, ptr, cap = _emit_args(out, k + 1, checksum)
         th = None if tables is None else (C.c_void_p * max(k, 1))(*[None if t is None else t.h for t in tables])
         rs = None if builds is None else (_Rel * max(k, 1))(*[_Rel() if r is None else r.c for r in builds])
         self._check(lib().hj3d_select_nested(self.h, ptr_in, n, k, None if base is None else C.byref(base.c), th, rs,

@@ -28,8 +28,8 @@ pytestmark = pytest.mark.gpu
 HEAVY_OUT = 8192        # nested.hip:257  kHeavyOut: more outputs than this make a slot heavy
 HEAVY_SPAN = 1024       # nested.hip:434  kHeavySpan: flattened heavy outputs per wave and round
 OFFSETS_ROUND = 1024    # nested.hip:392,401  k_heavy_offsets: heavy slots scanned per round (one workgroup)
-UN2_CHUNK = 2048        # unnest2.hip:24  kChunk: outputs per workgroup and step
-UN2_CHUNK_SLOTS = 2048  # unnest2.hip:25  kChunkSlots: slot offsets of a chunk staged in LDS
+UN2_CHUNK = 2048        # nested_tuple.hpp:62  kChunk: outputs per workgroup and step
+UN2_CHUNK_SLOTS = 2048  # nested_tuple.hpp:63  kChunkSlots: slot offsets of a chunk staged in LDS
 INLINE2 = 64            # exp4.hip:27  kInline2: larger products are queued for the heavy kernels
 BLOCK, WAVE = 256, 64   # hj3d_internal.hpp:31  kBlock, hj3d_device.hpp:13  kWave
 NOREF = X.NOREF
@@ -51,7 +51,7 @@ def heavy_flat_round(n_cus):  # outputs k_expand_heavy_flat covers before a wave
     return heavy_groups(n_cus) * (BLOCK // WAVE) * HEAVY_SPAN
 
 
-def un2_round(n_cus):  # unnest2.hip:146: outputs k_un2_expand covers before a workgroup takes its next chunk
+def un2_round(n_cus):  # unnest2.hip:108: outputs k_un2_expand covers before a workgroup takes its next chunk
     return 8 * n_cus * UN2_CHUNK
 
 
@@ -265,7 +265,7 @@ def unnest2_input(a, key_s, key_t, refs_s, refs_t, n_mains):
 
 def chunk_slots(prod) -> np.ndarray:
     """nq of every k_un2_expand chunk: the slots from the one holding the chunk's first output to the
-    one holding its last (unnest2.hip:79-81)."""
+    one holding its last (for_each_output, nested_tuple.hpp:92-94)."""
     ooff = np.concatenate([[0], np.cumsum(prod)])
     total = int(ooff[-1])
     first = np.arange(0, total, UN2_CHUNK)
@@ -407,7 +407,7 @@ def test_unnest2_capacity_across_rounds(ctx, rounds_case, where):
 
 def test_unnest2_product_beyond_32_bits(ctx):
     """One pair of groups of 65,600 x 65,600 rows: the triple index k inside the slot passes 2^32, where
-    k_un2_expand splits it with 64-bit arithmetic (unnest2.hip:97-103). sum_b and sum_c both move if
+    k_un2_expand splits it with 64-bit arithmetic (unnest2.hip:61-67). sum_b and sum_c both move if
     k / |S|, k % |S| is wrong there. Counters against the analytic form (no enumeration)."""
     HOT = 65_600
     rng = np.random.default_rng(401)

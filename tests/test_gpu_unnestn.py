@@ -23,7 +23,7 @@ from test_gpu_unnest import CANARY, EXP4, NOREF, PATHS, dev, host, on_path
 
 pytestmark = pytest.mark.gpu
 
-# unnestn.hip's constants (a change there must fail the branch assertions below, not empty the cases)
+# the constants of k_unn_expand's walk, nested_tuple.hpp (a change there must fail the branch assertions below, not empty the cases)
 CHUNK = 2048        # kChunk: outputs per workgroup and step
 CHUNK_SLOTS = 2048  # kChunkSlots: slot offsets of a chunk staged in LDS
 
