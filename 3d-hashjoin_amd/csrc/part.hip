@@ -359,7 +359,9 @@ __global__ __launch_bounds__(kBlock) void k_expect(RelView p, uint64_t n_keys, c
   for (uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x; i < p.n; i += uint64_t(gridDim.x) * kBlock) {
     const uint32_t k = p.key(i);
     if (k >= n_keys) continue;
-    const uint32_t x = swap ? inv[k] : p.row(i), y = swap ? p.row(i) : inv[k];
+    const uint32_t br = inv[k];
+    if (br == kInvalid) continue;  // no build row holds k: no partner, no pair
+    const uint32_t x = swap ? br : p.row(i), y = swap ? p.row(i) : br;
     const uint64_t h = pair_hash(x, y);
     a[0] += 1;
     a[1] += x;

@@ -794,7 +794,10 @@ hj3d_status hj3d_gen_exp4_ref(uint32_t log2R, uint32_t alpha, uint32_t mult_a, u
                               uint32_t* Sa, uint32_t* Ta, uint64_t* card);
 /* Expected key/FK join aggregates WITHOUT a hash table (full-size verification of the
  * key/FK plans): `build` holds unique keys in [0, n_keys); every probe tuple's partner row is
- * inv[key], inv being the inverse of the build key column. Accumulates {n_out, sum_a, sum_b,
+ * inv[key], inv being the inverse of the build key column. Probe keys outside [0, n_keys) are
+ * skipped, and keys of the domain that no build row holds join with nothing (a build side may
+ * cover only part of the domain: a rank's shard, an R shorter than n_keys); build row id
+ * 0xFFFFFFFF is reserved (it marks "no row" in inv). Accumulates {n_out, sum_a, sum_b,
  * sum_h, xor_h} (u64 each) into res_dev (zero it first). Orientation: a = probe row,
  * b = build row; with swap != 0, a = build row, b = probe row (plans that build on the FK side). */
 hj3d_status hj3d_expected_fk_join(hj3d_ctx* ctx, const hj3d_rel* build, const hj3d_rel* probe, uint64_t n_keys,

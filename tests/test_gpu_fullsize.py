@@ -5,7 +5,8 @@ For a key/FK join every S tuple has exactly one partner, the R row whose key equ
 hj3d_expected_fk_join computes that pair set WITHOUT a hash table (inverse permutation of
 R.k), so the join's cardinality and its order-independent pair checksums are checked
 bit-exactly at full size. Comparison counts are checked against the oracle at 1e6 / 1e7
-on the same generator."""
+on the same generator. The generators and hj3d_expected_fk_join themselves are verified in
+tests/test_gpu_generators.py, against the numpy model of tests/gen_model.py."""
 import numpy as np
 import pytest
 
