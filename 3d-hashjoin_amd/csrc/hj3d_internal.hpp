@@ -12,6 +12,7 @@
 
 #include "hj3d.h"
 #include "hj3d_device.hpp"
+#include "sel_pred.hpp"
 
 namespace hj3d {
 // Kernel launches of this library, process-wide (hj3d_launch_count: the bench reports launches per
@@ -208,64 +209,14 @@ struct hj3d_table {
 
 namespace hj3d {
 
-// Selection predicate (hj3d_sel_pred conjunction) as a kernel argument, and its evaluation on the
-// u32 tuple word(s) it reads (AlgSelection::step, algebra.hh:295-300).
-struct SelArgs {
-  uint32_t npred = 0;
-  hj3d_sel_pred p[HJ3D_SEL_MAX];
-};
-__device__ __forceinline__ bool sel_one(const hj3d_sel_pred& p, uint32_t w) {
-  const int64_t v = p.is_signed ? int64_t(int32_t(w)) : int64_t(w);
-  switch (p.op) {
-    case HJ3D_SEL_LT: return v < p.lo;
-    case HJ3D_SEL_LE: return v <= p.lo;
-    case HJ3D_SEL_GT: return v > p.lo;
-    case HJ3D_SEL_GE: return v >= p.lo;
-    case HJ3D_SEL_EQ: return v == p.lo;
-    case HJ3D_SEL_NE: return v != p.lo;
-    default: return v >= p.lo && v < p.hi;  // HJ3D_SEL_RANGE
-  }
-}
+// Selection predicates: SelArgs, sel_one, SelRange and sel_args live in sel_pred.hpp (host-checkable).
+// A conjunction evaluated on the u32 tuple word(s) it reads (AlgSelection::step, algebra.hh:295-300):
 __device__ __forceinline__ bool sel_eval(const RelView& r, const SelArgs& a, uint64_t i) {
   const char* t = r.base + i * r.stride;
   bool ok = true;
   for (uint32_t k = 0; k < a.npred; ++k)
     ok = ok && sel_one(a.p[k], *reinterpret_cast<const uint32_t*>(t + a.p[k].word_off));
   return ok;
-}
-// One predicate as an inclusive range test on the word read as int32 / uint32 (inverted for !=):
-// the form the probe partitioner evaluates in its hot loop.
-struct SelRange {
-  uint32_t word_off = 0, is_signed = 0, invert = 0, pad = 0;
-  int64_t lo = 0, hi = -1;
-  __device__ __forceinline__ bool test(uint32_t w) const {
-    const int64_t v = is_signed ? int64_t(int32_t(w)) : int64_t(w);
-    return (v >= lo && v <= hi) != (invert != 0);
-  }
-  static bool from(const SelArgs& a, SelRange* r) {
-    if (a.npred != 1) return false;
-    const hj3d_sel_pred& p = a.p[0];
-    const int64_t mn = p.is_signed ? INT32_MIN : 0, mx = p.is_signed ? INT32_MAX : int64_t(UINT32_MAX);
-    r->word_off = p.word_off;
-    r->is_signed = p.is_signed != 0;
-    r->invert = 0;
-    switch (p.op) {
-      case HJ3D_SEL_LT: r->lo = mn; r->hi = p.lo - 1; break;
-      case HJ3D_SEL_LE: r->lo = mn; r->hi = p.lo; break;
-      case HJ3D_SEL_GT: r->lo = p.lo + 1; r->hi = mx; break;
-      case HJ3D_SEL_GE: r->lo = p.lo; r->hi = mx; break;
-      case HJ3D_SEL_EQ: r->lo = p.lo; r->hi = p.lo; break;
-      case HJ3D_SEL_NE: r->lo = p.lo; r->hi = p.lo; r->invert = 1; break;
-      default: r->lo = p.lo; r->hi = p.hi - 1; break;  // RANGE
-    }
-    return true;
-  }
-};
-inline SelArgs sel_args(const hj3d_sel_pred* preds, uint32_t npred) {
-  SelArgs a{};
-  a.npred = npred;
-  for (uint32_t k = 0; k < npred; ++k) a.p[k] = preds[k];
-  return a;
 }
 
 // ---- decoupled look-back (exclusive_scan_u32, k_pk_build) ----

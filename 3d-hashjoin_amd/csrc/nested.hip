@@ -932,8 +932,10 @@ hipError_t nested_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, u
 }
 
 bool radix_nested_applicable(const hj3d_ctx* ctx, const hj3d_table* t, uint64_t n_probe) {
-  return t->desc.kind == HJ3D_NESTED && !ctx->force_direct && n_probe >= ctx->radix_min && t->nb_local >= 64 &&
-         n_probe < (1ull << 32) && t->n_mains > 0;
+  // (n_probe > 0: with HJ3D_OPT_RADIX_MIN = 0 an empty probe side, e.g. a selection nothing passed,
+  // would reach the partitioner's geometry with zero tiles and divide by its zero workgroups)
+  return t->desc.kind == HJ3D_NESTED && !ctx->force_direct && n_probe >= ctx->radix_min && n_probe > 0 &&
+         t->nb_local >= 64 && n_probe < (1ull << 32) && t->n_mains > 0;
 }
 
 hipError_t radix_nested_probe(hj3d_ctx* ctx, const hj3d_table* t, const hj3d_rel& r, uint32_t flags, void* out,

@@ -216,7 +216,10 @@ FUSED_CASES = [
     ("empty_range", [(2, "range", 30, 30)]),
     ("on_key_word", [(1, "<", 1000)]),
     ("two_preds_unfused", [(2, ">=", 10), (2, "<", 60)]),
+    ("gt_unsigned_above_int32", [(2, ">", 3 * 2**30, None, False)]),  # full-range words from here on
+    ("lt_signed_bit31_words", [(2, "<", -2**30)]),
 ]
+FULL_RANGE_WORDS = ("gt_unsigned_above_int32", "lt_signed_bit31_words")
 
 
 @pytest.mark.gpu
@@ -232,7 +235,10 @@ def test_gpu_probe_sel_bit_exact(ctx, name, preds, unique):
     R = O.tuples3(Rk, np.zeros_like(Rk))
     S = O.tuples3(np.arange(nS, dtype=np.uint32), Sa)
     S[:, 2] = np.random.default_rng(5).integers(-5, 100, size=nS).astype(np.int32).view(np.uint32)
+    if name in FULL_RANGE_WORDS:
+        S[:, 2] = np.random.default_rng(5).integers(0, 2**32, size=nS, dtype=np.uint64).astype(np.uint32)
     sel_h = O.select(S, 1, preds)
+    assert name not in FULL_RANGE_WORDS or 0 < len(sel_h) < nS
     exp = O.chain_plan(R, 0, sel_h, 0, nR, unique, prow=1)
     ctx.radix_min(1 << 12)  # the partitioned (fusing) path at this size
     tab = hj3d.Table(ctx, hj3d.HJ3D_CHAIN, nR)
