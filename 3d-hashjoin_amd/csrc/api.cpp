@@ -384,6 +384,7 @@ void hj3d_ctx_destroy(hj3d_ctx* ctx) {
   ctx->res.release();
   ctx->resn.release();
   ctx->resa.release();
+  ctx->resg.release();
   ctx->misc.release();
   ctx->ctl.release();
   ctx->scan_status.release();
@@ -445,6 +446,10 @@ hj3d_status hj3d_ctx_set_option(hj3d_ctx* ctx, int option, int64_t value) {
     case HJ3D_OPT_PK_STAGE:
       if (value < 0 || value > 0xFFFFFFFFll) return fail(ctx, HJ3D_EINVAL, "HJ3D_OPT_PK_STAGE: >= 0");
       ctx->pk_stage = uint32_t(value);
+      return HJ3D_OK;
+    case HJ3D_OPT_GBY_FORM:
+      if (value < 0 || value > 3) return fail(ctx, HJ3D_EINVAL, "HJ3D_OPT_GBY_FORM: 0..3");
+      ctx->gby_form = int(value);
       return HJ3D_OK;
     default: return fail(ctx, HJ3D_EINVAL, "hj3d_ctx_set_option: unknown option");
   }
@@ -1119,6 +1124,73 @@ hj3d_status hj3d_agg_nested_result(hj3d_ctx* ctx, hj3d_aggn_res* out) {
   }
   // every input tuple has a row; those past the buffer were not written
   if (ctx->resa_n > ctx->resa_cap) return fail(ctx, HJ3D_EOVERFLOW, "hj3d_agg_nested: output buffer too small");
+  return HJ3D_OK;
+}
+
+hj3d_status hj3d_agg_grouped(hj3d_ctx* ctx, const void* nested_dev, uint64_t n, uint32_t k,
+                             const hj3d_table* const* tables, uint32_t by_slot, const hj3d_rel* base,
+                             const hj3d_gby_spec* specs, uint32_t nspec, uint32_t flags, void* out_dev,
+                             uint64_t out_cap) {
+  const char* const me = "hj3d_agg_grouped";
+  if (!ctx || !tables || !specs) return HJ3D_EINVAL;
+  if (k < 1 || k > HJ3D_NEST_MAX) return fail_in(ctx, me, "k must be 1 .. HJ3D_NEST_MAX");
+  if (by_slot < 1 || by_slot > k) return fail_in(ctx, me, "by_slot must be 1 .. k");
+  if (const hj3d_status st = tables_given(ctx, me, tables, k); st != HJ3D_OK) return st;
+  if (nspec < 1 || nspec > HJ3D_AGG_MAX) return fail_in(ctx, me, "nspec must be 1 .. HJ3D_AGG_MAX");
+  if (flags & ~HJ3D_PROBE_ACCUMULATE) return fail_in(ctx, me, "flags other than ACCUMULATE");
+  if (const hj3d_status st = tables_nested(ctx, me, tables, k); st != HJ3D_OK) return st;
+  if (const hj3d_status st = nested_input_ok(ctx, me, nested_dev, n); st != HJ3D_OK) return st;
+  if (const hj3d_status st = out_aligned(ctx, me, out_dev, 8); st != HJ3D_OK) return st;
+  bool base_word = false;
+  for (uint32_t q = 0; q < nspec; ++q) {
+    const hj3d_gby_spec& sp = specs[q];
+    if (sp.op > HJ3D_AGG_MAX_) return fail_in(ctx, me, "unknown aggregate");
+    if (sp.slot > k) return fail_in(ctx, me, "a spec's slot beyond k");
+    if (sp.op == HJ3D_AGG_COUNT && sp.slot != 0) return fail_in(ctx, me, "COUNT takes slot 0");
+    if (sp.slot >= 1 && (!sp.gcol || (uintptr_t(sp.gcol) & 7))) return fail_in(ctx, me, "a spec without its column");
+    if (sp.slot == 0 && sp.op != HJ3D_AGG_COUNT) {
+      if (!rel_ok(base) || base->row_off != HJ3D_ROW_IMPLICIT)
+        return fail_in(ctx, me, "a base-word spec needs a valid base relation (implicit rows only)");
+      if ((sp.word_off & 3) || uint64_t(sp.word_off) + 4 > base->stride) return fail_in(ctx, me, "word_off outside the tuple");
+      base_word = true;
+    }
+  }
+  if (const hj3d_status st = resolve_all(ctx, me, tables, k); st != HJ3D_OK) return st;
+  for (uint32_t q = 0; q < nspec; ++q)  // (the main-record counts are known once the builds are finished)
+    if (specs[q].slot >= 1 && specs[q].gcol_n < tables[specs[q].slot - 1]->n_mains)
+      return fail_in(ctx, me, "a column shorter than its table's main records");
+  const uint64_t n_mains = tables[by_slot - 1]->n_mains;
+  if (n_mains && !out_dev) return fail_in(ctx, me, "no output buffer");
+  if (out_cap < n_mains) return fail(ctx, HJ3D_EOVERFLOW, "hj3d_agg_grouped: fewer output rows than main records");
+  if (hipError_t ae = ctx->resg.ensure(kAggnWords * sizeof(uint64_t)); ae != hipSuccess) return from_hip(ctx, ae, me);
+  PhaseTimer tm(ctx, HJ3D_T_PROBE);
+  const hipError_t e = agg_grouped(ctx, nested_dev, n, k, tables, by_slot, base_word ? base : nullptr, specs, nspec, flags,
+                                   out_dev, ctx->resg.as<uint64_t>(), ctx->stream);
+  ctx->resg_n = n;
+  ctx->resg_nspec = nspec;
+  for (uint32_t q = 0; q < nspec; ++q) {
+    ctx->resg_op[q] = specs[q].op;
+    ctx->resg_sgn[q] = specs[q].is_signed != 0;
+  }
+  return from_hip(ctx, e, me);
+}
+
+hj3d_status hj3d_agg_grouped_result(hj3d_ctx* ctx, hj3d_aggn_res* out) {
+  if (!ctx || !out) return HJ3D_EINVAL;
+  std::memset(out, 0, sizeof(*out));
+  if (!ctx->resg.p) return fail(ctx, HJ3D_EINVAL, "hj3d_agg_grouped_result: no hj3d_agg_grouped before it");
+  uint64_t h[kAggnWords];
+  if (const hj3d_status st = read_slot(ctx, "hj3d_agg_grouped_result", ctx->resg.p, h, kAggnWords); st != HJ3D_OK) return st;
+  out->n_in = ctx->resg_n;
+  out->n_live = h[0];
+  if (magnitude_exceeded(h[kAggnFlag], h[kAggnHi], h[kAggnLo]))
+    return fail(ctx, HJ3D_EUNSUPPORTED, "hj3d_agg_grouped: a tuple's product or c_top reaches 2^63");
+  out->c_top = h[kAggnCTop];
+  for (uint32_t q = 0; q < ctx->resg_nspec; ++q) {
+    const uint32_t op = ctx->resg_op[q];
+    const bool mm = op == HJ3D_AGG_MIN || op == HJ3D_AGG_MAX_;
+    out->total[q] = agg_total_decode(h[(mm ? kAggnMm : kAggnAdd) + q], op, ctx->resg_sgn[q]);
+  }
   return HJ3D_OK;
 }
 

@@ -162,6 +162,11 @@ struct hj3d_ctx {
   hj3d::DevBuf resa;
   uint64_t resa_n = 0, resa_cap = ~0ull;
   uint32_t resa_nspec = 0, resa_op[HJ3D_AGG_MAX] = {0}, resa_sgn[HJ3D_AGG_MAX] = {0};
+  // hj3d_agg_grouped: the same for its own result slot (kAggnWords words, hj3d_agg_nested's layout)
+  hj3d::DevBuf resg;
+  uint64_t resg_n = 0;
+  uint32_t resg_nspec = 0, resg_op[HJ3D_AGG_MAX] = {0}, resg_sgn[HJ3D_AGG_MAX] = {0};
+  int gby_form = 0;  // HJ3D_OPT_GBY_FORM: 0 = chosen per call, 1 direct, 2 LDS column, 3 LDS cache
   hipError_t ensure_ctl() {
     if (ctl.p) return hipSuccess;
     hipError_t e = ctl.ensure(128 * sizeof(uint64_t));  // 8 control words; [64, 128): store sink
@@ -443,6 +448,13 @@ hipError_t agg_nested(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t k, con
                       const hj3d_agg_spec* specs, uint32_t nspec, uint32_t flags, void* out, uint64_t out_cap,
                       uint64_t* res_dev, hipStream_t s);
 uint64_t agg_total_decode(uint64_t word, uint32_t op, uint32_t is_signed);
+// agg_grouped.hip: hj3d_agg_grouped, the same tuples reduced per main ref of tables[by_slot - 1] into the
+// column out (n_mains rows of nspec u64; initialised here unless flags has ACCUMULATE); validated arguments,
+// resolved tables, base null unless a spec reads a base word. res: the kAggnWords words of ctx->resg (the
+// layout of hj3d_agg_nested's slot), cleared here. The form: ctx->gby_form.
+hipError_t agg_grouped(hj3d_ctx* ctx, const void* in, uint64_t n, uint32_t k, const hj3d_table* const* tables,
+                       uint32_t by_slot, const hj3d_rel* base, const hj3d_gby_spec* specs, uint32_t nspec,
+                       uint32_t flags, void* out, uint64_t* res_dev, hipStream_t s);
 // exp4.hip
 hipError_t probe2(hj3d_ctx* ctx, const hj3d_table* ts, const hj3d_table* tt, const hj3d_rel& r, uint32_t flags,
                   void* out, uint64_t out_cap, uint64_t* res_dev, hipStream_t s);

@@ -33,6 +33,7 @@ OPT_PK_SLICE, OPT_PK_STAGE, OPT_PK_BUILD, OPT_NESTED_PK, OPT_SYNC_BUILD = 8, 9, 
 OPT_RP_UNFUSED = 15
 OPT_DIAG_GBAR = 16
 OPT_DIAG_LOOKBACK = 17
+OPT_GBY_FORM = 18
 SEL_LT, SEL_LE, SEL_GT, SEL_GE, SEL_EQ, SEL_NE, SEL_RANGE = range(7)
 SEL_MAX = 4
 NSEL_BASE, NSEL_COUNT, NSEL_FIRST = range(3)  # where a nested-tuple predicate takes its u32 (select_nested)
@@ -88,6 +89,11 @@ class _NSelPred(C.Structure):
 
 class _AggSpec(C.Structure):
     _fields_ = [("op", C.c_uint32), ("slot", C.c_uint32), ("is_signed", C.c_uint32), ("reserved", C.c_uint32),
+                ("gcol", C.c_void_p), ("gcol_n", C.c_uint64)]
+
+
+class _GbySpec(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("slot", C.c_uint32), ("is_signed", C.c_uint32), ("word_off", C.c_uint32),
                 ("gcol", C.c_void_p), ("gcol_n", C.c_uint64)]
 
 
@@ -178,6 +184,8 @@ def lib():
         "hj3d_group_agg": (st, [p, p, R, u32, u32, p, u64]),
         "hj3d_agg_nested": (st, [p, p, u64, u32, C.POINTER(p), C.POINTER(_AggSpec), u32, u32, p, u64]),
         "hj3d_agg_nested_result": (st, [p, C.POINTER(_AggNRes)]),
+        "hj3d_agg_grouped": (st, [p, p, u64, u32, C.POINTER(p), u32, R, C.POINTER(_GbySpec), u32, u32, p, u64]),
+        "hj3d_agg_grouped_result": (st, [p, C.POINTER(_AggNRes)]),
         "hj3d_gen_keys": (st, [p, p, u64, u32, u32, u64, u64, u64]),
         "hj3d_gen_fk": (st, [p, p, u64, u32, u32, u64, u32, u64]),
         "hj3d_gen_zipf": (st, [p, p, u64, u32, u32, u64, u32, C.c_double, u64]),
@@ -685,6 +693,77 @@ class Context:
         return {"n_in": r.n_in, "n_live": r.n_live, "c_top": r.c_top,
                 "total": list(r.total)[:getattr(self, "_aggn_nspec", AGG_MAX)], "overflow": st == HJ3D_EOVERFLOW}
 
+    # ---- the same aggregates per build key (join + GROUP BY a build key) ----
+    def agg_grouped(self, nested, tables, by: int, specs, base: Optional[Rel] = None, out=None,
+                    accumulate: bool = False, fetch: bool = True):
+        """hj3d_agg_grouped: agg_nested's aggregates over the tuples of `nested`, reduced per group of
+        tables[by - 1] (by: slot 1..k, the grouping ref). specs: agg_nested's tuples, plus (op, "base",
+        word[, signed]) with op "sum" | "min" | "max": word `word` of base row a of `base` (implicit rows;
+        required then, and a tuple whose a is not a row of it is dead), read as int32 (signed, default) or
+        uint32; SUM weighs it with the tuple's COUNT. Returns (column, result): the (n_mains, len(specs))
+        int64 device tensor indexed by main ref of the by-table (allocated on the context stream when `out`
+        is None; else a view of `out`, a contiguous (cap, len(specs)) int64 device tensor;
+        `out` itself with fetch=False, which reads nothing back; Hj3dError(HJ3D_EOVERFLOW) when cap is below
+        the main-record count), and agg_grouped_result()'s dict, or None with fetch=False. accumulate: the column is not initialised and the call folds into what is
+        there (the result restarts either way)."""
+        torch = _torch()
+        k = len(tables)
+        if not 1 <= k <= HJ3D_NEST_MAX:
+            raise ValueError(f"agg_grouped takes 1..{HJ3D_NEST_MAX} tables")
+        if not 1 <= by <= k:
+            raise ValueError(f"by must be a slot 1..{k}")
+        if not 1 <= len(specs) <= AGG_MAX:
+            raise ValueError(f"agg_grouped takes 1..{AGG_MAX} specs")
+        ptr_in, n = _words(nested, k + 1, "nested")
+        arr = (_GbySpec * len(specs))()
+        for i, sp in enumerate(specs):
+            if sp[0] not in AGG_OPS:
+                raise ValueError(f"unknown aggregate {sp[0]!r} (count, sum, min, max)")
+            if sp[0] == "count":
+                arr[i] = _GbySpec(AGG_COUNT, 0, 0, 0, None, 0)
+                continue
+            signed = sp[3] if len(sp) > 3 else True
+            if isinstance(sp[1], str):
+                if sp[1] != "base" or base is None:
+                    raise ValueError('a spec reads a word of the base row as (op, "base", word[, signed]), with base given')
+                arr[i] = _GbySpec(AGG_OPS[sp[0]], 0, int(bool(signed)), 4 * int(sp[2]), None, 0)
+                continue
+            col = sp[2]
+            if not col.is_cuda or col.dtype != torch.int64 or col.dim() != 2 or col.shape[1] != 3 or not col.is_contiguous():
+                raise ValueError("a spec's column must be a contiguous (n_mains, 3) int64 device tensor")
+            arr[i] = _GbySpec(AGG_OPS[sp[0]], int(sp[1]), int(bool(signed)), 0, col.data_ptr() if col.shape[0] else None,
+                              col.shape[0])
+        n_mains = None
+        if out is None:  # (the main-record count is read from the table: synchronous)
+            n_mains = tables[by - 1].size()[1]
+            with self.on_stream():
+                out = torch.empty((n_mains, len(specs)), dtype=torch.int64, device=f"cuda:{self.device}")
+        elif not out.is_cuda or out.dtype != torch.int64 or out.dim() != 2 or out.shape[1] != len(specs) or \
+                not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous (cap, {len(specs)}) int64 device tensor")
+        th = (C.c_void_p * k)(*[t.h for t in tables])
+        self._check(lib().hj3d_agg_grouped(self.h, ptr_in, n, k, th, by, None if base is None else C.byref(base.c), arr,
+                                           len(specs), PROBE_ACCUMULATE if accumulate else 0,
+                                           out.data_ptr() if out.shape[0] else None, out.shape[0]), "hj3d_agg_grouped")
+        self._gby_nspec = len(specs)
+        if n_mains is None and fetch:
+            n_mains = tables[by - 1].size()[1]
+        return (out if n_mains is None else out[:n_mains]), (self.agg_grouped_result() if fetch else None)
+
+    def agg_grouped_result(self) -> dict:
+        """The last agg_grouped's result: n_in, n_live, c_top and total (one per spec, as
+        agg_nested_result() defines them over that call's tuples: the reduce of the column over all
+        groups). Raises Hj3dError(HJ3D_EUNSUPPORTED) when a tuple's product or c_top reaches 2^63."""
+        r = _AggNRes()
+        self._check(lib().hj3d_agg_grouped_result(self.h, C.byref(r)), "hj3d_agg_grouped_result")
+        return {"n_in": r.n_in, "n_live": r.n_live, "c_top": r.c_top,
+                "total": list(r.total)[:getattr(self, "_gby_nspec", AGG_MAX)]}
+
+    def gby_form(self, f: int = 0):
+        """A/B switch and test hook (HJ3D_OPT_GBY_FORM): agg_grouped's kernel form, 0 = automatic, 1 = direct
+        global atomics, 2 = the column in LDS (when it fits, else 1), 3 = the LDS cache of groups."""
+        self.set_option(OPT_GBY_FORM, int(f))
+
     def packed_probe(self, on: bool = True):
         """A/B switch: the unique chaining probe on packed pairs (default) or on (hash, row) pairs."""
         self.set_option(OPT_PACKED_PROBE, int(on))
@@ -1120,4 +1199,4 @@ class Table:
 
 from .plans import (EXP1_PLANS, exp1_plan, exp1_plan_sharded, exp1_relations_ref, exp4_plan,  # noqa: E402,F401
                     exp4_plan_chained, exp4_plan_sharded, exp4_relations_ref, merge_exp4, merge_shard_stats, num_buckets_exp1,
-                    num_distinct_sharded, star_plan_aggregate, star_plan_chained)
+                    num_distinct_sharded, star_plan_aggregate, star_plan_chained, star_plan_grouped)

@@ -377,6 +377,36 @@ def star_plan_aggregate(ctx: Context, R, builds, nb, keys, aggregate, out=None, 
     return res
 
 
+@_on_ctx_stream
+def star_plan_grouped(ctx: Context, R, builds, nb, keys, by, aggregate, filters=None, out=None) -> dict:
+    """star_plan_aggregate's chain and aggregates, grouped by the key of build level `by` (0-based, as in
+    filters): SELECT build[by].key, aggregates FROM the join GROUP BY build[by].key, without unnesting.
+    aggregate: star_plan_aggregate's list plus (op, "base", word[, signed]), a word of R itself. The
+    Table.group_agg columns are made once per (level, word, signed); Context.agg_grouped then reduces per main
+    ref of table `by`. Returns Context.agg_grouped_result()'s dict plus the per-level lists and "column": the
+    (n_mains, len(aggregate)) int64 device tensor indexed by main ref of table `by` (a view of `out` when
+    given)."""
+    tables, cur, levels = _star_chain(ctx, R, builds, nb, keys, filters)
+    cols, specs = {}, []
+    for sp in aggregate:
+        if sp[0] == "count":
+            specs.append(("count",))
+            continue
+        signed = sp[3] if len(sp) > 3 else True
+        if sp[1] == "base":
+            specs.append((sp[0], "base", sp[2], signed))
+            continue
+        level, word = sp[1], sp[2]
+        if (level, word, signed) not in cols:
+            rel, kw = builds[level]
+            cols[(level, word, signed)] = tables[level].group_agg(Rel(rel, key_word=kw), word, signed, fetch=False)[0]
+        specs.append((sp[0], level + 1, cols[(level, word, signed)], signed))
+    column, res = ctx.agg_grouped(cur, tables, by + 1, specs, base=Rel(R, key_word=keys[by]), out=out)
+    res.update(levels)
+    res["column"] = column
+    return res
+
+
 EXP4_SUM = ("c_probe_rs", "c_probe_rs_cmp", "c_probe_rt", "c_probe_rt_cmp", "c_unnest_1", "c_unnest_2", "c_top",
             "sum_a", "sum_b", "sum_c", "sum_h")
 

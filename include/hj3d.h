@@ -33,7 +33,8 @@
  *                              AlgUnnestHt, over stored nested tuples   algebra.hh:278-358 on 435-459,
  *                                                                     main_algebra_example.cc:226-234, 305-316
  *   hj3d_group_agg,            (no counterpart) aggregates over the rows stored nested tuples would unnest
- *   hj3d_agg_nested            to, without running AlgUnnestHt::step   algebra.hh:490-541
+ *   hj3d_agg_nested,           to, without running AlgUnnestHt::step   algebra.hh:490-541
+ *   hj3d_agg_grouped           (per build group, per tuple or in total, per group of the join result)
  *
  * Semantics kept bit-exact with the reference: hash = murmur3 fmix32 (util/hasht.hh:52-61),
  * bucket = hash % num_buckets, and every counter the reference reports (match counts,
@@ -244,7 +245,12 @@ enum {
    * partition's main-record base waits on its predecessors' published counts, at most 0.2 s, after
    * which the build gives up and the sort build replaces the table). Partition 0 then never
    * publishes and the wait limit is this many ticks, so every such build gives up (tests). */
-  HJ3D_OPT_DIAG_LOOKBACK = 17
+  HJ3D_OPT_DIAG_LOOKBACK = 17,
+  /* HJ3D_OPT_GBY_FORM (0..3, default 0): which kernel form hj3d_agg_grouped takes. 0 = chosen per call;
+   * 1 = direct (one global atomic per live tuple and spec); 2 = the whole column kept in LDS by every
+   * workgroup (when it does not fit: form 1); 3 = a direct-mapped LDS cache of groups in front of the
+   * global atomics. Every form gives the same column (tests and A/B). */
+  HJ3D_OPT_GBY_FORM = 18
 };
 hj3d_status hj3d_ctx_set_option(hj3d_ctx* ctx, int option, int64_t value);
 /* Timing events for a host's own phase timers (the bench's build / probe boundaries): HIP events
@@ -762,6 +768,54 @@ hj3d_status hj3d_agg_nested(hj3d_ctx* ctx, const void* nested_dev, uint64_t n, u
                             const hj3d_table* const* tables, const hj3d_agg_spec* specs, uint32_t nspec,
                             uint32_t flags, void* out_dev, uint64_t out_cap);
 hj3d_status hj3d_agg_nested_result(hj3d_ctx* ctx, hj3d_aggn_res* out);
+
+/* ---- the same aggregates per build key: join + GROUP BY a build key ----
+ * SELECT s.key, COUNT(*), SUM(r.x), MIN(t.y) FROM R join S join T GROUP BY s.key. The main ref of the by-table
+ * is the group id, so the aggregates are reduced into a column indexed by that main ref: the column shape
+ * hj3d_group_agg produces and hj3d_agg_nested consumes. */
+typedef struct {
+  uint32_t op, slot;  /* HJ3D_AGG_*; slot 1..k: a group's hj3d_gagg column; slot 0: COUNT, or (op != COUNT) a word
+                         of the base row                                                                        */
+  uint32_t is_signed; /* MIN / MAX order, and the extension of a base word                                      */
+  uint32_t word_off;  /* slot 0, op != COUNT: byte offset of the u32 in the base tuple; else 0                   */
+  const void* gcol;   /* slot >= 1: hj3d_gagg column of tables[slot - 1] (device, 8-byte aligned); else NULL     */
+  uint64_t gcol_n;    /* its records; must be >= that table's main-record count                                 */
+} hj3d_gby_spec;
+/* hj3d_agg_grouped: nested_dev holds n tuples {u32 a, u32 ref_1 .. ref_k} exactly as for hj3d_agg_nested, and
+ * liveness is hj3d_agg_nested's: a tuple with any ref not below its table's main-record count is dead. If any
+ * spec has slot 0 with op != COUNT, `base` is required (implicit rows) and a tuple whose a is not a row of
+ * base (a - row_base outside [0, n)) is dead too, hj3d_select_nested's rule; without such a spec base may be
+ * NULL and a is opaque. Nothing is read through a dead tuple.
+ * Per tuple and spec, with P = prod |G_j|: for slot >= 1 and for COUNT exactly the value hj3d_agg_nested
+ * defines; for a base-word spec SUM = ext(w) * P mod 2^64 and MIN / MAX = ext(w), w the u32 at word_off of base
+ * row a, sign- (is_signed) or zero-extended to 64 bits.
+ * out_dev is a column of n_mains(tables[by_slot - 1]) rows of nspec u64 (8-byte aligned): row m, field s = the
+ * sum mod 2^64 (COUNT, SUM), or the min / max in the spec's order, of spec s's values over the live tuples with
+ * ref_by_slot == m; a group without a live tuple gets 0 / 0 / the identities of hj3d_group_agg. The operator
+ * initialises the column itself. out_cap (rows) below the main-record count gives HJ3D_EOVERFLOW and nothing is
+ * written (hj3d_group_agg's rule); nothing is ever written at or beyond out_dev + 8 nspec out_cap.
+ * flags: HJ3D_PROBE_ACCUMULATE only. With it the column is not initialised and the call folds into what is
+ * there (a strand issued in chunks, several inputs grouped into one column); the result slot restarts on every
+ * call either way.
+ * hj3d_agg_grouped_result: n_in, n_live, c_top and total[s] as hj3d_agg_nested defines them over this call's
+ * tuples, so total[s] is the reduce of column s over all groups (without ACCUMULATE). The magnitude rule is
+ * hj3d_agg_nested's: a P, or c_top, at or beyond 2^63 gives HJ3D_EUNSUPPORTED with only n_in and n_live set,
+ * and the column is then unspecified. The result has a slot of its own: the probe, hj3d_unnestn and
+ * hj3d_agg_nested result slots are not touched.
+ * HJ3D_EINVAL: any other flag; a null ctx / tables / entry of tables / specs; a chaining table; k outside
+ * 1 .. HJ3D_NEST_MAX; by_slot outside 1 .. k; nspec outside 1 .. HJ3D_AGG_MAX; an unknown op; slot > k; COUNT with
+ * slot != 0; slot >= 1 with a null gcol or gcol_n below that table's main-record count; slot 0 with op != COUNT
+ * and base null, invalid or with explicit rows, or word_off not a multiple of 4 or outside the tuple;
+ * nested_dev not 4-byte or out_dev / gcol not 8-byte aligned; n && !nested_dev; out_dev == NULL with a
+ * non-empty by-table; n >= 2^32; hj3d_agg_grouped_result before any hj3d_agg_grouped.
+ * Asynchronous on the context stream; pending nested builds of the given tables are finished first, as by a
+ * probe. A cleared by-table writes nothing and reports n_live = 0. HJ3D_OPT_GBY_FORM picks the kernel form;
+ * every form gives the same column. */
+hj3d_status hj3d_agg_grouped(hj3d_ctx* ctx, const void* nested_dev, uint64_t n, uint32_t k,
+                             const hj3d_table* const* tables, uint32_t by_slot, const hj3d_rel* base,
+                             const hj3d_gby_spec* specs, uint32_t nspec, uint32_t flags, void* out_dev,
+                             uint64_t out_cap);
+hj3d_status hj3d_agg_grouped_result(hj3d_ctx* ctx, hj3d_aggn_res* out);
 
 /* ---- synthetic key/FK relations generated on the device (bench / full-size checks) ----
  * R.k = a seeded bijective permutation of [0, n_keys) (keys for global rows
